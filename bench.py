@@ -20,6 +20,13 @@ Launch (driver contract):
 Under torchrun, rank 0 runs the kubelet stack managing GPUs 0..N-1 (one
 kubelet per node is the product architecture); other ranks only participate
 in barriers. Weak scaling: each extra GPU adds one pod per wave.
+
+A plain run sets up, warms up, times the K waves and prints one JSON result
+line. `--dump-outputs DIR` also writes what the last timed wave returned
+(pod_state.npy, wave_summary.npy, workload_report.npy; float32; no timings,
+so two builds can be compared file for file). `--full` is where measurements
+beyond the headline figure belong; none exist today (`--burst` and
+`--settle-gap` select other configurations and are runs of their own).
 """
 
 from __future__ import annotations
@@ -55,9 +62,79 @@ def _barrier(dist, device_sync: bool):
         torch.cuda.synchronize()
 
 
+# Columns of pod_state.npy (one row per pod of the last timed wave, in
+# creation order), read off the pod object the apiserver held at Ready.
+POD_STATE_COLUMNS = (
+    "phase_running", "cond_pod_scheduled", "cond_initialized", "cond_ready",
+    "cond_containers_ready", "n_containers", "containers_ready",
+    "containers_started", "containers_running", "restart_count",
+    "gpus_requested", "gpus_bound",
+)
+
+
+def _pod_state_row(pod):
+    status = pod.get("status", {})
+    conds = {c["type"]: float(c["status"] == "True")
+             for c in status.get("conditions", [])}
+    cs = status.get("containerStatuses", [])
+    requested = sum(
+        int(c.get("resources", {}).get("limits", {}).get("amd.com/gpu", 0))
+        for c in pod["spec"]["containers"])
+    return [
+        float(status.get("phase") == "Running"),
+        conds.get("PodScheduled", 0.0), conds.get("Initialized", 0.0),
+        conds.get("Ready", 0.0), conds.get("ContainersReady", 0.0),
+        float(len(cs)),
+        float(sum(bool(c.get("ready")) for c in cs)),
+        float(sum(bool(c.get("started")) for c in cs)),
+        float(sum("running" in c.get("state", {}) for c in cs)),
+        float(sum(int(c.get("restartCount", 0)) for c in cs)),
+        float(requested), float(len(_bound_gpu_ids(pod))),
+    ]
+
+
+def _bound_gpu_ids(pod):
+    ids = pod["metadata"].get("annotations", {}).get("amd.com/gpu-ids", "")
+    return [int(x) for x in ids.split(",") if x.strip()]
+
+
+def _outputs_of_wave(ready_pods, logs, use_gpu):
+    """What a caller of one wave receives, as arrays: each pod's state at
+    Ready, how many distinct GPUs the wave was bound to, and what each pod's
+    workload reported (devices it verified its kernel on). Timings are left
+    out: they differ from run to run and are in the result line."""
+    import numpy as np
+
+    return {
+        "pod_state": np.array([_pod_state_row(p) for p in ready_pods],
+                              dtype=np.float32),
+        # which GPUs a wave gets depends on timing (placement prefers GPUs
+        # whose last pod left a while ago); how many distinct ones does not
+        "wave_summary": np.array(
+            [len(ready_pods),
+             len({i for p in ready_pods for i in _bound_gpu_ids(p)})],
+            dtype=np.float32),
+        "workload_report": np.array(
+            [[float(sum(line.startswith("podworker: dev ")
+                        and line.endswith(" ok")
+                        for line in text.splitlines())),
+              float(f"podworker: ready (gpus={1 if use_gpu else -1} ports=0)"
+                    in text)]
+             for text in logs], dtype=np.float32),
+    }
+
+
+def dump_outputs(outputs, directory):
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(directory, f"{name}.npy"), arr)
+
+
 def run_bench(n_gpus: int, steps: int, warmup: int, use_gpu: bool,
               hold_pods: bool = True, burst_size: int = 0,
-              settle_gap_s: float = 0.0):
+              settle_gap_s: float = 0.0, want_outputs: bool = False):
     from k8s_runpod_kubelet_amd.app import build_stack
     from k8s_runpod_kubelet_amd.config import Config
     from k8s_runpod_kubelet_amd.kube.client import NotFoundError
@@ -120,10 +197,22 @@ def run_bench(n_gpus: int, steps: int, warmup: int, use_gpu: bool,
         except NotFoundError:
             return True
 
-    def wave(tag, timeout_s=120.0):
+    captured = {}
+
+    def ready_log(name, timeout_s=5.0):
+        # the workload signals readiness just before it flushes stdout
+        deadline = time.monotonic() + timeout_s
+        while True:
+            text = stack.provider.get_container_logs("default", name)
+            if "podworker: ready" in text or time.monotonic() > deadline:
+                return text
+            time.sleep(0.002)
+
+    def wave(tag, timeout_s=120.0, capture=False):
         names = [f"bench-{tag}-{i}" for i in range(n_gpus)]
         created_at = {}
         ready_at = {}
+        ready_pods = {}
         for name in names:
             created_at[name] = time.monotonic()
             kube.create_pod("default", make_pod(name))
@@ -131,13 +220,22 @@ def run_bench(n_gpus: int, steps: int, warmup: int, use_gpu: bool,
         pending = set(names)
         while pending and time.monotonic() < deadline:
             for name in list(pending):
-                if pod_ready(name) is not None:
+                pod = pod_ready(name)
+                if pod is not None:
                     ready_at[name] = time.monotonic()
+                    ready_pods[name] = pod
                     pending.remove(name)
             if pending:
                 time.sleep(0.002)
         if pending:
             raise SystemExit(f"pods never became Ready: {sorted(pending)}")
+        if capture:
+            # the pods' logs go away with the pods; reading them is not part
+            # of the lifecycle, so its time is taken off the step
+            t_cap = time.monotonic()
+            captured["pods"] = [ready_pods[n] for n in names]
+            captured["logs"] = [ready_log(n) for n in names]
+            captured["seconds"] = time.monotonic() - t_cap
         for name in names:
             kube.delete_pod("default", name)
         pending = set(names)
@@ -210,6 +308,7 @@ def run_bench(n_gpus: int, steps: int, warmup: int, use_gpu: bool,
         for w in range(warmup):
             wave(f"w{w}")
         latencies = []
+        step_s = []
         t0 = time.monotonic()
         for k in range(steps):
             if settle_gap_s > 0:
@@ -218,8 +317,12 @@ def run_bench(n_gpus: int, steps: int, warmup: int, use_gpu: bool,
                 # (profiles/pw_timing.txt). Throughput output still includes
                 # the gaps — only the latency numbers are meaningful here.
                 time.sleep(settle_gap_s)
-            latencies.extend(wave(f"s{k}"))
-        elapsed = time.monotonic() - t0
+            t_step = time.monotonic()
+            latencies.extend(wave(
+                f"s{k}", capture=want_outputs and k == steps - 1))
+            step_s.append(time.monotonic() - t_step)
+        elapsed = time.monotonic() - t0 - captured.get("seconds", 0.0)
+        step_s[-1] -= captured.get("seconds", 0.0)
     finally:
         stack.stop()
 
@@ -227,11 +330,14 @@ def run_bench(n_gpus: int, steps: int, warmup: int, use_gpu: bool,
     from k8s_runpod_kubelet_amd.server import metrics as m
 
     return {
+        "outputs": (_outputs_of_wave(captured["pods"], captured["logs"],
+                                     use_gpu) if want_outputs else None),
         "mean_translate_ms": m.hist_mean_ms(m.translate_seconds),
         "mean_bind_ms": m.hist_mean_ms(m.bind_seconds),
         "mean_launch_ms": m.hist_mean_ms(m.launch_seconds),
         "mean_cgroup_ms": m.hist_mean_ms(m.cgroup_migrate_seconds),
         "elapsed_s": elapsed,
+        "step_ms": [s * 1000 for s in step_s],
         "pods": n_gpus * steps,
         "pods_per_sec": (n_gpus * steps) / elapsed,
         "p50_ready_ms": statistics.median(lat_ms),
@@ -254,7 +360,22 @@ def main():
     ap.add_argument("--settle-gap", type=float, default=0.0,
                     help="experiment only: sleep S s between waves so pod-Ready "
                          "reflects a settled GPU (throughput then meaningless)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last wave "
+                         "returned (pod states at Ready, GPUs bound, workload "
+                         "reports) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements a plain run leaves out; "
+                         "there are none yet: the burst and settle-gap "
+                         "configurations are separate runs behind their own "
+                         "options, so the result is that of a plain run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.burst:
+        ap.error("--dump-outputs applies to wave mode, not --burst")
 
     rank, world = _dist_env()
     dist = None
@@ -288,10 +409,16 @@ def main():
     if rank == 0:
         result = run_bench(args.gpus, args.steps, args.warmup, use_gpu,
                            burst_size=args.burst,
-                           settle_gap_s=args.settle_gap)
+                           settle_gap_s=args.settle_gap,
+                           want_outputs=bool(args.dump_outputs))
     _barrier(dist, device_sync)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(result["outputs"], args.dump_outputs)
 
     if rank == 0 and result is not None:
+        # burst mode times whole drains, not waves
+        step_ms = result.get("step_ms") or [
+            result["elapsed_s"] / args.steps * 1000]
         out = {
             "metric": "gpu_pods_scheduled_per_sec",
             # the exact composite metric BASELINE.json names; `value` carries
@@ -324,6 +451,12 @@ def main():
                 "burst_size": args.burst,
                 "settle_gap_s": args.settle_gap,
                 "pods_total": result["pods"],
+                # spread of the timed steps: one step's time is dominated
+                # by the workload's HIP context start, which varies by tens
+                # of ms from pod to pod, so a short run's mean is noisy
+                "step_ms_min": round(min(step_ms), 3),
+                "step_ms_p50": round(statistics.median(step_ms), 3),
+                "step_ms_max": round(max(step_ms), 3),
                 "mean_deploy_ms": round(result.get("mean_deploy_ms", 0), 3),
                 "mean_translate_ms": round(result.get("mean_translate_ms", 0), 3),
                 "mean_bind_ms": round(result.get("mean_bind_ms", 0), 3),
@@ -341,10 +474,12 @@ def main():
         # ROCm static destructors can std::terminate at interpreter exit
         # after a fully successful run (see tests/conftest.py note); the
         # result line is already printed and flushed — exit cleanly before
-        # they run.
-        sys.stdout.flush()
-        sys.stderr.flush()
-        os._exit(0)
+        # they run, but through the guard, so that atexit hooks registered
+        # at process start (instrumentation, coverage) still run; a bare
+        # os._exit() skipped them.
+        from k8s_runpod_kubelet_amd.utils.exit_guard import install
+
+        install(0)
 
 
 if __name__ == "__main__":

@@ -46,6 +46,36 @@ def test_bench_multi_gpu_cpu_mode():
     check_contract(out, 4, 2, 0)
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last wave's arrays (deterministic: no
+    timings) and --full is accepted; the result line keeps its contract."""
+    import numpy as np
+
+    bench_args = ["--gpus", "2", "--steps", "2", "--warmup", "0",
+                  "--mode", "cpu"]
+    dumps = []
+    for sub, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / sub
+        out = run_bench(bench_args + extra + ["--dump-outputs", str(d)])
+        check_contract(out, 2, 2, 0)
+        dumps.append({p.name: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert sorted(a) == ["pod_state.npy", "wave_summary.npy",
+                         "workload_report.npy"]
+    state = a["pod_state.npy"]
+    assert state.dtype == np.float32 and state.shape[0] == 2
+    # every pod of the wave was Running+Ready with its one GPU bound
+    assert (state[:, [0, 3, 4]] == 1.0).all()
+    assert (state[:, [10, 11]] == 1.0).all()
+    # two pods, on two distinct GPUs
+    assert a["wave_summary.npy"].tolist() == [2.0, 2.0]
+    # CPU mode: the workload reports ready, and no device
+    assert a["workload_report.npy"].tolist() == [[0.0, 1.0], [0.0, 1.0]]
+    for name in a:
+        assert a[name].dtype == np.float32
+        assert np.array_equal(a[name], b[name]), name
+
+
 def test_bench_under_torchrun_world2():
     # The driver launches N>1 via torch.distributed.run; verify that shape
     # works on CPU (gloo, 127.0.0.1 rendezvous).

@@ -259,6 +259,9 @@ def _raw_layer(members):
                 tf.addfile(info)
             elif kind == "dir":
                 info.type = tarfile.DIRTYPE
+                # TarInfo defaults to 0644; a directory without the search
+                # bit is only traversable by root
+                info.mode = 0o755
                 tf.addfile(info)
             else:
                 data = t.encode()

@@ -221,6 +221,10 @@ def test_adoption_preserves_credentials_and_deadline(synthetic_ledger,
     activeDeadlineSeconds and terminationGracePeriodSeconds must survive a
     kubelet restart — a crash-restarting container was being relaunched as
     root with default grace/deadline."""
+    import os
+
+    if os.geteuid() != 0:
+        pytest.skip("needs root to drop to another uid")
     rt = ProcessRuntime(synthetic_ledger, tmp_state_dir, enable_cgroups=False)
     st = rt.deploy(DeployParams(
         pod_key="default-cred", name="cred",
@@ -498,10 +502,21 @@ def test_adoption_rearms_kill_timer_for_terminating(synthetic_ledger,
         termination_grace_s=1.0,
         containers=[ContainerSpec(
             name="main", command=["/bin/sh"],
-            args=["-c", "trap '' TERM; while :; do sleep 1; done"])],
+            args=["-c", "trap '' TERM; echo immune; "
+                        "while :; do sleep 1; done"])],
     ))
     wait_status(rt, st.id, PodStatus.RUNNING)
     pid = rt.get_detailed_status(st.id).containers[0].pid
+    # RUNNING only says the shell was spawned; a TERM that lands before it
+    # has run `trap` would kill it
+    logp = os.path.join(tmp_state_dir, "logs", f"{st.id}-main.log")
+    deadline = time.time() + 10
+    while time.time() < deadline:
+        if os.path.exists(logp) and "immune" in open(logp).read():
+            break
+        time.sleep(0.02)
+    else:
+        raise AssertionError("container never installed its TERM trap")
     rt.terminate(st.id)  # TERM ignored; grace timer armed
     rt.close()           # kubelet "dies": timer cancelled
     assert os.path.exists(f"/proc/{pid}")

@@ -258,8 +258,11 @@ def test_exec_on_pending_pod_reports_state(provider):
 def test_exec_targets_named_container(provider, process_runtime):
     """kubectl exec -c <name>: the exec runs with the targeted container's
     credentials/confinement (multi-container pod)."""
+    import os
     import urllib.request
 
+    if os.geteuid() != 0:
+        pytest.skip("needs root to drop to another uid")
     prov, _, kube = provider
     prov.runtime = process_runtime
     pod = make_pod("multi", containers=[
