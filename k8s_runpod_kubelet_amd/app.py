@@ -45,6 +45,7 @@ class Stack:
     inventory: Optional[Inventory] = None
     ledger: Optional[Ledger] = None
     recorder: Optional[EventRecorder] = None
+    diagnostics: Optional[object] = None  # gpu.diagnostics.DiagnosticsManager
     _stopped: bool = field(default=False, repr=False)
 
     def start(self, serve_http: bool = True) -> None:
@@ -57,6 +58,7 @@ class Stack:
                 ledger=self.ledger,
                 admin_token=self.config.admin_token
                 or os.environ.get("AMDVK_ADMIN_TOKEN", ""),
+                diagnostics=self.diagnostics,
             )
             self.health.start()
             self.api_server = KubeletApiServer(
@@ -134,6 +136,16 @@ def build_stack(
     provider = Provider(client, config, runtime, ledger=ledger, inventory=inventory)
     recorder = EventRecorder(client)
     provider.recorder = recorder
+    diagnostics = None
+    if ledger is not None and inventory is not None:
+        from .gpu.diagnostics import DiagnosticsManager
+
+        # Constructing the manager runs nothing: checks start only from the
+        # opt-in triggers or the operator endpoint.
+        diagnostics = DiagnosticsManager(ledger, inventory, config,
+                                         recorder=recorder,
+                                         node_name=config.node_name)
+        provider.diagnostics = diagnostics
     informer = PodInformer(
         client, config.node_name, resync_interval_s=config.reconcile_interval_s
     )
@@ -154,6 +166,7 @@ def build_stack(
         inventory=inventory,
         ledger=ledger,
         recorder=recorder,
+        diagnostics=diagnostics,
     )
 
 

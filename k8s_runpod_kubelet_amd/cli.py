@@ -62,6 +62,21 @@ def build_parser() -> argparse.ArgumentParser:
                         "time (token via AMDVK_REGISTRY_TOKEN)")
     p.add_argument("--gpu-count-override", type=int, default=-1,
                    help="force synthetic GPU inventory (CPU-only dev)")
+    # Active GPU self-test (gpu/diagnostics.py); unset flags leave the
+    # provider-config values alone.
+    p.add_argument("--gpu-check-on-start", action="store_true", default=None,
+                   help="self-test every idle GPU before serving")
+    p.add_argument("--gpu-check-interval", default=None,
+                   help="re-check idle GPUs this often (e.g. 6h; 0 = off)")
+    p.add_argument("--gpu-check-bytes", default=None,
+                   help="HBM region per check (e.g. 4G; default 1G)")
+    p.add_argument("--gpu-check-timeout", default=None,
+                   help="per-check timeout (default 60s)")
+    p.add_argument("--gpu-check-min-copy-gbs", type=float, default=None,
+                   help="fail a check whose copy bandwidth is below this "
+                        "(GB/s; 0 = off)")
+    p.add_argument("--gpu-check-parallel", type=int, default=None,
+                   help="checks running at once (default 2)")
     p.add_argument("--fake-apiserver", action="store_true",
                    help="start an in-process fake Kubernetes apiserver and "
                         "connect to it (self-contained demo; no cluster "
@@ -106,6 +121,22 @@ def main(argv=None) -> int:
     cfg.image_isolation = args.image_isolation
     if args.image_registry:
         cfg.image_registry = args.image_registry
+    if args.gpu_check_on_start:
+        cfg.gpu_check_on_start = True
+    if args.gpu_check_interval is not None:
+        cfg.gpu_check_interval_s = parse_duration_s(
+            args.gpu_check_interval, cfg.gpu_check_interval_s)
+    if args.gpu_check_bytes is not None:
+        from .gpu.diagnostics import parse_size
+
+        cfg.gpu_check_bytes = parse_size(args.gpu_check_bytes)
+    if args.gpu_check_timeout is not None:
+        cfg.gpu_check_timeout_s = parse_duration_s(
+            args.gpu_check_timeout, cfg.gpu_check_timeout_s)
+    if args.gpu_check_min_copy_gbs is not None:
+        cfg.gpu_check_min_copy_gbs = args.gpu_check_min_copy_gbs
+    if args.gpu_check_parallel is not None:
+        cfg.gpu_check_parallel = args.gpu_check_parallel
 
     validate_environment()
     fake_srv = None

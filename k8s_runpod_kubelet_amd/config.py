@@ -118,6 +118,16 @@ class Config:
     # dead device; the GPU itself is cordoned by the health re-probe
     evict_on_gpu_failure: bool = True
 
+    # Active GPU self-test (gpu/diagnostics.py: HBM pattern, copy bandwidth,
+    # MFMA). Off by default; a failed check fences the GPU until an operator
+    # re-check passes.
+    gpu_check_on_start: bool = False       # check idle GPUs before serving
+    gpu_check_interval_s: float = 0.0      # periodic re-check; 0 = off
+    gpu_check_bytes: int = 1 << 30         # HBM region per check
+    gpu_check_timeout_s: float = 60.0
+    gpu_check_min_copy_gbs: float = 0.0    # copy-bandwidth floor; 0 = off
+    gpu_check_parallel: int = 2            # checks running at once
+
     # GPU inventory overrides (mostly for tests / CPU-only dev)
     gpu_count_override: int = -1
     gpu_vram_gb_override: int = -1

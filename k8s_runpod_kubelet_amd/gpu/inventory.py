@@ -37,6 +37,11 @@ class Gpu:
     temperature_mc: int = -1
     ras_uncorrectable: int = 0
     healthy: bool = True
+    # Active self-test verdict (gpu/diagnostics.py). Separate from the
+    # passive ``healthy`` bit, which refresh_dynamic() overwrites each tick.
+    diag_ok: bool = True
+    diag_reason: str = ""
+    diag_last: Optional[dict] = None
     # peer GPU index -> xGMI link weight/bandwidth (MB/s); absent = no link
     xgmi_peers: Dict[int, int] = field(default_factory=dict)
 

@@ -43,7 +43,7 @@ class GpuState:
 
     @property
     def schedulable(self) -> bool:
-        return self.gpu.healthy and not self.cordoned
+        return self.gpu.healthy and self.gpu.diag_ok and not self.cordoned
 
     @property
     def occupied(self) -> bool:
@@ -77,6 +77,13 @@ class Ledger:
         with self._lock:
             for gpu in self.inventory.gpus:
                 if gpu.index in self.states:
+                    old = self.states[gpu.index].gpu
+                    if old is not gpu:
+                        # a re-discovered record must not forget a failed
+                        # self-test
+                        gpu.diag_ok = old.diag_ok
+                        gpu.diag_reason = old.diag_reason
+                        gpu.diag_last = old.diag_last
                     self.states[gpu.index].gpu = gpu
                 else:
                     self.states[gpu.index] = GpuState(gpu=gpu)
@@ -164,3 +171,20 @@ class Ledger:
                 return False
             state.cordoned = cordoned
             return True
+
+    def set_diag(self, idx: int, ok: bool, reason: str = "",
+                 result: Optional[dict] = None) -> bool:
+        """Record an active self-test verdict (gpu/diagnostics.py) under the
+        ledger lock. Returns False for an unknown GPU index."""
+        with self._lock:
+            state = self.states.get(idx)
+            if state is None:
+                return False
+            state.gpu.diag_ok = ok
+            state.gpu.diag_reason = reason
+            state.gpu.diag_last = result
+            return True
+
+    def get_state(self, idx: int) -> Optional[GpuState]:
+        with self._lock:
+            return self.states.get(idx)

@@ -55,3 +55,17 @@ def podworker_binary() -> str:
             )
         build_mod.build_podworker()
     return str(path)
+
+
+def gpucheck_binary() -> str:
+    from . import build as build_mod
+
+    path = build_mod.gpucheck_path()
+    if not path.exists():
+        if gpu_box():
+            raise RuntimeError(
+                "gpucheck binary missing on a GPU box — build it with "
+                "`python -m k8s_runpod_kubelet_amd.ops.build`"
+            )
+        build_mod.build_gpucheck()
+    return str(path)

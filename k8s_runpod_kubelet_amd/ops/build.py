@@ -4,6 +4,8 @@ Builds (next to this file, so the .so/binary travel with the repo snapshot):
 - ``_native.*.so``      — pybind11 extension (probe + launcher), plain C++.
 - ``podworker/podworker`` — HIP workload binary for gfx950 (hipcc
   cross-compiles without a GPU; built with --offload-arch=gfx950).
+- ``gpucheck/gpucheck``   — HIP diagnostic binary for gfx950 (HBM pattern,
+  copy bandwidth, MFMA self-test), built the same way.
 
 Run: ``python -m k8s_runpod_kubelet_amd.ops.build`` (or via
 ``__graft_entry__.build()``).
@@ -21,6 +23,7 @@ from pathlib import Path
 OPS_DIR = Path(__file__).resolve().parent
 CSRC = OPS_DIR / "csrc"
 PODWORKER_DIR = OPS_DIR / "podworker"
+GPUCHECK_DIR = OPS_DIR / "gpucheck"
 
 GFX_ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -42,6 +45,10 @@ def native_ext_path() -> Path:
 
 def podworker_path() -> Path:
     return PODWORKER_DIR / "podworker"
+
+
+def gpucheck_path() -> Path:
+    return GPUCHECK_DIR / "gpucheck"
 
 
 def _content_stamp(sources: list[Path], cmd: list[str]) -> str:
@@ -107,9 +114,27 @@ def build_podworker(force: bool = False) -> Path:
     return out
 
 
+def build_gpucheck(force: bool = False) -> Path:
+    out = gpucheck_path()
+    src = GPUCHECK_DIR / "gpucheck.hip"
+    header = GPUCHECK_DIR / "gpucheck_pattern.h"
+    cmd = [
+        HIPCC, f"--offload-arch={GFX_ARCH}", "-O2", "-std=c++17",
+        str(src), "-o", str(out),
+    ]
+    stamp_file = GPUCHECK_DIR / ".gpucheck.buildstamp"
+    stamp = _content_stamp([src, header], cmd)
+    if not force and _is_fresh(out, stamp_file, stamp):
+        return out
+    _run(cmd)
+    stamp_file.write_text(stamp + "\n")
+    return out
+
+
 def build_all(force: bool = False) -> None:
     build_native(force=force)
     build_podworker(force=force)
+    build_gpucheck(force=force)
 
 
 if __name__ == "__main__":

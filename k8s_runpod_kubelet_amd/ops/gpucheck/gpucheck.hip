@@ -1,0 +1,688 @@
+// gpucheck — active GPU self-test run between tenants.
+//
+// Tests visible device 0 (the caller scopes visibility with
+// ROCR_VISIBLE_DEVICES) in three stages:
+//   1. HBM fill + verify with a hashed 16-byte pattern and its complement,
+//   2. device-to-device copy bandwidth,
+//   3. an exact-integer MFMA self-test (bf16 32x32x16, no memory loads).
+// Prints exactly one JSON object as the last stdout line and exits with a
+// stage-specific code:
+//   0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, 21 MFMA mismatch,
+//   22 copy bandwidth below --min-copy-gbs.
+// `--cpu` runs the HBM stage as host loops over malloc'ed memory and makes no
+// HIP call, so the CLI, JSON and mismatch localisation are testable without
+// a GPU.
+//
+// Build: hipcc --offload-arch=gfx950 -O2 -std=c++17 gpucheck.hip -o gpucheck
+
+#include <hip/hip_runtime.h>
+
+#include <errno.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <vector>
+
+#include "gpucheck_pattern.h"
+
+using gpucheck::Vec16;
+
+namespace {
+
+struct HipError {
+  std::string what;
+};
+
+#define HIP_CHECK(expr)                                                  \
+  do {                                                                   \
+    hipError_t err_ = (expr);                                            \
+    if (err_ != hipSuccess)                                              \
+      throw HipError{std::string(#expr) + ": " + hipGetErrorString(err_)}; \
+  } while (0)
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kBlock = 256;
+constexpr size_t kMaxGrid = 2048;
+constexpr uint64_t kNoBad = ~0ull;
+constexpr size_t kCacheResidentBelow = 512ull << 20;
+
+// ---------------------------------------------------------------- kernels
+
+__device__ inline u32x4 pattern_vec(uint64_t seed, uint32_t pass,
+                                    uint64_t index) {
+  const Vec16 v = gpucheck::pattern(seed, pass, index);
+  u32x4 x;
+  x.x = static_cast<unsigned int>(v.lo);
+  x.y = static_cast<unsigned int>(v.lo >> 32);
+  x.z = static_cast<unsigned int>(v.hi);
+  x.w = static_cast<unsigned int>(v.hi >> 32);
+  return x;
+}
+
+// One 16-byte vector per lane per trip; consecutive lanes write consecutive
+// vectors. All indices are size_t: regions exceed 4 GiB.
+template <bool kNonTemporal>
+__global__ __launch_bounds__(kBlock) void hbm_fill(u32x4* __restrict__ p,
+                                                   size_t nvec,
+                                                   uint64_t base_index,
+                                                   uint64_t seed,
+                                                   uint32_t pass) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+       i < nvec; i += stride) {
+    const u32x4 x = pattern_vec(seed, pass, base_index + i);
+    if (kNonTemporal)
+      __builtin_nontemporal_store(x, &p[i]);
+    else
+      p[i] = x;
+  }
+}
+
+// counters[0] += bad vectors, counters[1] = min(bad vector index). One
+// integer atomic pair per wave, and only from waves that saw a mismatch.
+__global__ __launch_bounds__(kBlock) void hbm_verify(
+    const u32x4* __restrict__ p, size_t nvec, uint64_t base_index,
+    uint64_t seed, uint32_t pass, unsigned long long* counters) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  unsigned long long bad = 0;
+  unsigned long long first = kNoBad;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+       i < nvec; i += stride) {
+    const u32x4 got = p[i];
+    const u32x4 want = pattern_vec(seed, pass, base_index + i);
+    if (got.x != want.x || got.y != want.y || got.z != want.z ||
+        got.w != want.w) {
+      ++bad;
+      if (i < first) first = i;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    bad += __shfl_xor(bad, off);
+    const unsigned long long other = __shfl_xor(first, off);
+    first = other < first ? other : first;
+  }
+  if ((threadIdx.x & 63) == 0 && bad != 0) {
+    atomicAdd(&counters[0], bad);
+    atomicMin(&counters[1], first);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void vec_copy(u32x4* __restrict__ dst,
+                                                   const u32x4* __restrict__ src,
+                                                   size_t nvec) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+       i < nvec; i += stride)
+    dst[i] = src[i];
+}
+
+// Each wave computes one 32x32 tile D = A.B with K = 128 from operands
+// generated in registers, then stores it to out[wave][row][col]. Lane l
+// (r = l & 31, h = l >> 5) holds A[r][8h+j] and B[8h+j][r] of each 16-wide
+// k-step in element j; accumulator register g is D[(g&3)+8(g>>2)+4h][r].
+__global__ __launch_bounds__(kBlock) void mfma_selftest(float* __restrict__ out,
+                                                        uint32_t nwaves,
+                                                        uint64_t seed) {
+  const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  // Wave-uniform: surplus waves of the last workgroup leave whole, so every
+  // MFMA below runs with a full EXEC mask.
+  if (wave >= nwaves) return;
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 31;
+  const int h = lane >> 5;
+  const uint64_t key_a = gpucheck::mfma_key(seed, wave, 0);
+  const uint64_t key_b = gpucheck::mfma_key(seed, wave, 1);
+  f32x16 acc;
+  for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
+#pragma unroll
+  for (int s = 0; s < gpucheck::kMfmaK / 16; ++s) {
+    s16x8 a, b;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = 16 * s + 8 * h + j;
+      a[j] = static_cast<short>(
+          gpucheck::bf16_bits_small_int(gpucheck::mfma_a(key_a, r, k)));
+      b[j] = static_cast<short>(
+          gpucheck::bf16_bits_small_int(gpucheck::mfma_b(key_b, k, r)));
+    }
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+        __builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0,
+        0, 0);
+  }
+  float* tile = out + static_cast<size_t>(wave) * (32 * 32);
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
+    tile[row * 32 + r] = acc[g];
+  }
+}
+
+// ---------------------------------------------------------------- options
+
+struct Options {
+  bool cpu = false;
+  size_t bytes = 1ull << 30;
+  uint32_t passes = 2;
+  uint64_t base_index = 0;
+  uint64_t seed = 0x6770756368656B31ull;
+  double min_copy_gbs = 0.0;
+  long mfma_waves = -1;  // -1: 8 x multiProcessorCount
+  bool inject = false;
+  size_t inject_offset = 0;
+  int inject_bit = 0;
+  bool dump_pattern = false;
+};
+
+bool parse_u64(const char* s, uint64_t* out, bool allow_suffix) {
+  if (s == nullptr || *s == '\0' || *s == '-' || *s == '+') return false;
+  errno = 0;
+  char* end = nullptr;
+  unsigned long long v = strtoull(s, &end, 0);
+  if (errno != 0 || end == s) return false;
+  int shift = 0;
+  if (allow_suffix && *end != '\0') {
+    switch (*end) {
+      case 'k': case 'K': shift = 10; break;
+      case 'm': case 'M': shift = 20; break;
+      case 'g': case 'G': shift = 30; break;
+      case 't': case 'T': shift = 40; break;
+      default: return false;
+    }
+    ++end;
+    if (*end == 'i') ++end;
+    if (*end == 'B' || *end == 'b') ++end;
+  }
+  if (*end != '\0') return false;
+  if (shift && v > (~0ull >> shift)) return false;
+  *out = v << shift;
+  return true;
+}
+
+bool parse_double(const char* s, double* out) {
+  if (s == nullptr || *s == '\0') return false;
+  errno = 0;
+  char* end = nullptr;
+  double v = strtod(s, &end);
+  if (errno != 0 || end == s || *end != '\0' || !(v >= 0.0)) return false;
+  *out = v;
+  return true;
+}
+
+int usage(const char* why, const char* arg) {
+  fprintf(stderr,
+          "gpucheck: %s%s%s\n"
+          "usage: gpucheck [--cpu] [--bytes N[K|M|G]] [--passes P] "
+          "[--base-index N] [--seed S]\n"
+          "                [--min-copy-gbs X] [--mfma-waves W] "
+          "[--inject-flip OFFSET:BIT]\n",
+          why, arg ? " " : "", arg ? arg : "");
+  return 2;
+}
+
+// Returns 0 on success, 2 on a usage error.
+int parse_args(int argc, char** argv, Options* o) {
+  for (int i = 1; i < argc; ++i) {
+    const std::string a = argv[i];
+    auto next = [&]() -> const char* {
+      return (i + 1 < argc) ? argv[++i] : nullptr;
+    };
+    uint64_t u = 0;
+    if (a == "--cpu") {
+      o->cpu = true;
+    } else if (a == "--dump-pattern") {
+      o->dump_pattern = true;
+    } else if (a == "--bytes") {
+      if (!parse_u64(next(), &u, true)) return usage("bad value for", "--bytes");
+      o->bytes = static_cast<size_t>(u);
+    } else if (a == "--passes") {
+      if (!parse_u64(next(), &u, false) || u == 0 || u > 1024)
+        return usage("bad value for", "--passes");
+      o->passes = static_cast<uint32_t>(u);
+    } else if (a == "--base-index") {
+      if (!parse_u64(next(), &u, false))
+        return usage("bad value for", "--base-index");
+      o->base_index = u;
+    } else if (a == "--seed") {
+      if (!parse_u64(next(), &u, false)) return usage("bad value for", "--seed");
+      o->seed = u;
+    } else if (a == "--min-copy-gbs") {
+      if (!parse_double(next(), &o->min_copy_gbs))
+        return usage("bad value for", "--min-copy-gbs");
+    } else if (a == "--mfma-waves") {
+      if (!parse_u64(next(), &u, false) || u == 0 || u > 65536)
+        return usage("bad value for", "--mfma-waves");
+      o->mfma_waves = static_cast<long>(u);
+    } else if (a == "--inject-flip") {
+      const char* v = next();
+      const char* colon = v ? strchr(v, ':') : nullptr;
+      uint64_t bit = 0;
+      if (colon == nullptr ||
+          !parse_u64(std::string(v, colon - v).c_str(), &u, false) ||
+          !parse_u64(colon + 1, &bit, false) || bit > 7)
+        return usage("bad value for", "--inject-flip");
+      o->inject = true;
+      o->inject_offset = static_cast<size_t>(u);
+      o->inject_bit = static_cast<int>(bit);
+    } else {
+      return usage("unknown argument", a.c_str());
+    }
+  }
+  if (o->bytes < 16) o->bytes = 16;
+  o->bytes &= ~static_cast<size_t>(15);
+  if (o->inject && o->inject_offset >= o->bytes)
+    return usage("--inject-flip offset is outside the region", nullptr);
+  return 0;
+}
+
+// ----------------------------------------------------------------- report
+
+struct Report {
+  std::string device = "cpu";
+  int compute_units = 0;
+  // HBM
+  uint64_t mismatch_vectors = 0;
+  bool have_first_bad = false;
+  uint64_t first_bad_offset = 0;
+  uint32_t first_bad_pass = 0;
+  Vec16 first_bad_xor{0, 0};
+  double write_gbs = 0, read_gbs = 0;
+  double write_gbs_plain = 0, write_gbs_nontemporal = 0;
+  const char* store_variant = "plain";
+  std::vector<std::string> pattern_dump;
+  // bandwidth
+  const char* bandwidth = "skipped";
+  double copy_gbs = 0;
+  // MFMA
+  const char* mfma = "skipped";
+  long mfma_waves = 0, mfma_bad_waves = 0, mfma_first_bad_wave = -1;
+};
+
+std::string hex128(const Vec16& v) {
+  char buf[40];
+  snprintf(buf, sizeof(buf), "%016llx%016llx",
+           static_cast<unsigned long long>(v.hi),
+           static_cast<unsigned long long>(v.lo));
+  return buf;
+}
+
+double gbs(double bytes, double seconds) {
+  return seconds > 0 ? bytes / 1e9 / seconds : 0.0;
+}
+
+// ---------------------------------------------------------------- backends
+
+struct Backend {
+  virtual ~Backend() {}
+  virtual int store_variants() const = 0;
+  // Both return elapsed seconds.
+  virtual double fill(uint32_t pass, int variant) = 0;
+  virtual double verify(uint32_t pass, uint64_t* bad, uint64_t* first) = 0;
+  virtual Vec16 read_vec(size_t i) = 0;
+  virtual void write_vec(size_t i, const Vec16& v) = 0;
+};
+
+struct CpuBackend : Backend {
+  const Options& o;
+  size_t nvec;
+  Vec16* mem;
+  explicit CpuBackend(const Options& opt)
+      : o(opt), nvec(opt.bytes / 16),
+        mem(static_cast<Vec16*>(malloc(opt.bytes))) {}
+  ~CpuBackend() override { free(mem); }
+  int store_variants() const override { return 1; }
+  static double since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0)
+        .count();
+  }
+  double fill(uint32_t pass, int) override {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t i = 0; i < nvec; ++i)
+      mem[i] = gpucheck::pattern(o.seed, pass, o.base_index + i);
+    return since(t0);
+  }
+  double verify(uint32_t pass, uint64_t* bad, uint64_t* first) override {
+    const auto t0 = std::chrono::steady_clock::now();
+    *bad = 0;
+    *first = kNoBad;
+    for (size_t i = 0; i < nvec; ++i) {
+      const Vec16 want = gpucheck::pattern(o.seed, pass, o.base_index + i);
+      if (mem[i].lo != want.lo || mem[i].hi != want.hi) {
+        ++*bad;
+        if (i < *first) *first = i;
+      }
+    }
+    return since(t0);
+  }
+  Vec16 read_vec(size_t i) override { return mem[i]; }
+  void write_vec(size_t i, const Vec16& v) override { mem[i] = v; }
+};
+
+unsigned int grid_for(size_t nvec) {
+  const size_t blocks = (nvec + kBlock - 1) / kBlock;
+  return static_cast<unsigned int>(std::max<size_t>(1, std::min(blocks, kMaxGrid)));
+}
+
+struct GpuTimer {
+  hipEvent_t start = nullptr, stop = nullptr;
+  void init() {
+    HIP_CHECK(hipEventCreate(&start));
+    HIP_CHECK(hipEventCreate(&stop));
+  }
+  void begin() { HIP_CHECK(hipEventRecord(start, 0)); }
+  double end() {
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(stop, 0));
+    HIP_CHECK(hipEventSynchronize(stop));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
+    return ms / 1e3;
+  }
+  ~GpuTimer() {
+    if (start) (void)hipEventDestroy(start);
+    if (stop) (void)hipEventDestroy(stop);
+  }
+};
+
+struct GpuBackend : Backend {
+  const Options& o;
+  size_t nvec;
+  u32x4* mem = nullptr;
+  unsigned long long* counters = nullptr;
+  GpuTimer timer;
+  explicit GpuBackend(const Options& opt) : o(opt), nvec(opt.bytes / 16) {
+    HIP_CHECK(hipMalloc(&mem, o.bytes));
+    HIP_CHECK(hipMalloc(&counters, 2 * sizeof(unsigned long long)));
+    timer.init();
+    // Load both fill kernels before anything is timed.
+    const size_t warm = std::min<size_t>(nvec, kBlock);
+    hipLaunchKernelGGL(hbm_fill<false>, dim3(1), dim3(kBlock), 0, 0, mem, warm,
+                       o.base_index, o.seed, 0u);
+    hipLaunchKernelGGL(hbm_fill<true>, dim3(1), dim3(kBlock), 0, 0, mem, warm,
+                       o.base_index, o.seed, 0u);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+  }
+  ~GpuBackend() override {
+    if (mem) (void)hipFree(mem);
+    if (counters) (void)hipFree(counters);
+  }
+  int store_variants() const override { return 2; }
+  double fill(uint32_t pass, int variant) override {
+    const dim3 grid(grid_for(nvec)), block(kBlock);
+    timer.begin();
+    if (variant == 1)
+      hipLaunchKernelGGL(hbm_fill<true>, grid, block, 0, 0, mem, nvec,
+                         o.base_index, o.seed, pass);
+    else
+      hipLaunchKernelGGL(hbm_fill<false>, grid, block, 0, 0, mem, nvec,
+                         o.base_index, o.seed, pass);
+    return timer.end();
+  }
+  double verify(uint32_t pass, uint64_t* bad, uint64_t* first) override {
+    const unsigned long long init[2] = {0ull, kNoBad};
+    HIP_CHECK(hipMemcpy(counters, init, sizeof(init), hipMemcpyHostToDevice));
+    timer.begin();
+    hipLaunchKernelGGL(hbm_verify, dim3(grid_for(nvec)), dim3(kBlock), 0, 0,
+                       mem, nvec, o.base_index, o.seed, pass, counters);
+    const double s = timer.end();
+    unsigned long long got[2];
+    HIP_CHECK(hipMemcpy(got, counters, sizeof(got), hipMemcpyDeviceToHost));
+    *bad = got[0];
+    *first = got[1];
+    return s;
+  }
+  Vec16 read_vec(size_t i) override {
+    Vec16 v;
+    HIP_CHECK(hipMemcpy(&v, mem + i, sizeof(v), hipMemcpyDeviceToHost));
+    return v;
+  }
+  void write_vec(size_t i, const Vec16& v) override {
+    HIP_CHECK(hipMemcpy(mem + i, &v, sizeof(v), hipMemcpyHostToDevice));
+  }
+};
+
+// ------------------------------------------------------------------ stages
+
+void run_hbm(Backend& be, const Options& o, Report* rep) {
+  const size_t nvec = o.bytes / 16;
+  const double bytes = static_cast<double>(o.bytes);
+  int variant = 0;
+  if (o.dump_pattern) {
+    for (size_t i = 0; i < std::min<size_t>(nvec, 4); ++i)
+      rep->pattern_dump.push_back(
+          hex128(gpucheck::pattern(o.seed, 0, o.base_index + i)));
+  }
+  for (uint32_t pass = 0; pass < o.passes; ++pass) {
+    double write_s;
+    if (pass == 0 && be.store_variants() > 1) {
+      // Both variants write the same data; keep the faster for later passes.
+      const double plain_s = be.fill(0, 0);
+      const double nt_s = be.fill(0, 1);
+      rep->write_gbs_plain = gbs(bytes, plain_s);
+      rep->write_gbs_nontemporal = gbs(bytes, nt_s);
+      variant = nt_s < plain_s ? 1 : 0;
+      rep->store_variant = variant ? "nontemporal" : "plain";
+      write_s = variant ? nt_s : plain_s;
+    } else {
+      write_s = be.fill(pass, variant);
+    }
+    rep->write_gbs = std::max(rep->write_gbs, gbs(bytes, write_s));
+    if (pass == 0 && o.inject) {
+      const size_t vi = o.inject_offset / 16;
+      Vec16 v = be.read_vec(vi);
+      unsigned char raw[16];
+      memcpy(raw, &v, 16);
+      raw[o.inject_offset % 16] ^= static_cast<unsigned char>(1u << o.inject_bit);
+      memcpy(&v, raw, 16);
+      be.write_vec(vi, v);
+    }
+    uint64_t bad = 0, first = kNoBad;
+    const double read_s = be.verify(pass, &bad, &first);
+    rep->read_gbs = std::max(rep->read_gbs, gbs(bytes, read_s));
+    rep->mismatch_vectors += bad;
+    if (bad != 0 && !rep->have_first_bad && first < nvec) {
+      const Vec16 got = be.read_vec(static_cast<size_t>(first));
+      const Vec16 want = gpucheck::pattern(o.seed, pass, o.base_index + first);
+      rep->have_first_bad = true;
+      rep->first_bad_offset = first * 16;
+      rep->first_bad_pass = pass;
+      rep->first_bad_xor = Vec16{got.lo ^ want.lo, got.hi ^ want.hi};
+    }
+  }
+  if (be.store_variants() == 1) rep->write_gbs_plain = rep->write_gbs;
+}
+
+void run_copy(GpuBackend& be, const Options& o, Report* rep) {
+  const size_t half = be.nvec / 2;
+  if (half == 0) return;  // a one-vector region has nothing to copy
+  const dim3 grid(grid_for(half)), block(kBlock);
+  std::vector<double> times;
+  for (int rep_i = 0; rep_i < 6; ++rep_i) {
+    be.timer.begin();
+    hipLaunchKernelGGL(vec_copy, grid, block, 0, 0, be.mem + half, be.mem, half);
+    const double s = be.timer.end();
+    if (rep_i > 0) times.push_back(s);  // the first repetition warms up
+  }
+  std::sort(times.begin(), times.end());
+  rep->copy_gbs = gbs(2.0 * 16.0 * static_cast<double>(half), times[times.size() / 2]);
+  rep->bandwidth =
+      (o.min_copy_gbs > 0 && rep->copy_gbs < o.min_copy_gbs) ? "fail" : "pass";
+}
+
+void run_mfma(const Options& o, int compute_units, Report* rep) {
+  const long nwaves = o.mfma_waves > 0 ? o.mfma_waves : 8L * compute_units;
+  const size_t nfloat = static_cast<size_t>(nwaves) * 32 * 32;
+  float* dev = nullptr;
+  HIP_CHECK(hipMalloc(&dev, nfloat * sizeof(float)));
+  HIP_CHECK(hipMemset(dev, 0xFF, nfloat * sizeof(float)));
+  const unsigned int blocks = static_cast<unsigned int>((nwaves + 3) / 4);
+  hipLaunchKernelGGL(mfma_selftest, dim3(blocks), dim3(kBlock), 0, 0, dev,
+                     static_cast<uint32_t>(nwaves), o.seed);
+  HIP_CHECK(hipGetLastError());
+  std::vector<float> host(nfloat);
+  HIP_CHECK(hipMemcpy(host.data(), dev, nfloat * sizeof(float),
+                      hipMemcpyDeviceToHost));
+  HIP_CHECK(hipFree(dev));
+
+  using gpucheck::kMfmaK;
+  std::vector<int> a(32 * kMfmaK), bt(32 * kMfmaK);
+  rep->mfma_waves = nwaves;
+  for (long w = 0; w < nwaves; ++w) {
+    const uint64_t key_a = gpucheck::mfma_key(o.seed, static_cast<uint32_t>(w), 0);
+    const uint64_t key_b = gpucheck::mfma_key(o.seed, static_cast<uint32_t>(w), 1);
+    for (int r = 0; r < 32; ++r)
+      for (int k = 0; k < kMfmaK; ++k) {
+        a[r * kMfmaK + k] = gpucheck::mfma_a(key_a, r, k);
+        bt[r * kMfmaK + k] = gpucheck::mfma_b(key_b, k, r);  // B transposed
+      }
+    const float* tile = host.data() + static_cast<size_t>(w) * 32 * 32;
+    bool bad = false;
+    for (int row = 0; row < 32 && !bad; ++row)
+      for (int col = 0; col < 32; ++col) {
+        int sum = 0;
+        for (int k = 0; k < kMfmaK; ++k)
+          sum += a[row * kMfmaK + k] * bt[col * kMfmaK + k];
+        // Every value is an integer of magnitude <= 1152, so equality of
+        // the floats is bit-exactness (NaN compares unequal and is caught).
+        if (!(tile[row * 32 + col] == static_cast<float>(sum))) {
+          bad = true;
+          break;
+        }
+      }
+    if (bad) {
+      if (rep->mfma_bad_waves == 0) rep->mfma_first_bad_wave = w;
+      ++rep->mfma_bad_waves;
+    }
+  }
+  rep->mfma = rep->mfma_bad_waves ? "fail" : "pass";
+}
+
+// ------------------------------------------------------------------- JSON
+
+std::string json_escape(const std::string& s) {
+  std::string out;
+  for (char c : s) {
+    if (c == '"' || c == '\\') {
+      out += '\\';
+      out += c;
+    } else if (static_cast<unsigned char>(c) < 0x20) {
+      out += ' ';
+    } else {
+      out += c;
+    }
+  }
+  return out;
+}
+
+void print_report(const Options& o, const Report& r, int code, double wall_s) {
+  const bool hbm_fail = r.mismatch_vectors != 0;
+  std::string failed;
+  auto add_failed = [&](const char* name) {
+    failed += failed.empty() ? "\"" : ",\"";
+    failed += name;
+    failed += "\"";
+  };
+  if (hbm_fail) add_failed("hbm");
+  if (!strcmp(r.mfma, "fail")) add_failed("mfma");
+  if (!strcmp(r.bandwidth, "fail")) add_failed("bandwidth");
+
+  printf("{\"tool\":\"gpucheck\",\"mode\":\"%s\",\"device\":\"%s\","
+         "\"compute_units\":%d,\"ok\":%s,\"exit_code\":%d,"
+         "\"failed_stages\":[%s],",
+         o.cpu ? "cpu" : "gpu", json_escape(r.device).c_str(), r.compute_units,
+         code == 0 ? "true" : "false", code, failed.c_str());
+  printf("\"bytes\":%zu,\"vectors\":%zu,\"passes\":%u,\"base_index\":%llu,"
+         "\"seed\":%llu,",
+         o.bytes, o.bytes / 16, o.passes,
+         static_cast<unsigned long long>(o.base_index),
+         static_cast<unsigned long long>(o.seed));
+  printf("\"hbm\":\"%s\",\"mismatch_vectors\":%llu,", hbm_fail ? "fail" : "pass",
+         static_cast<unsigned long long>(r.mismatch_vectors));
+  if (r.have_first_bad)
+    printf("\"first_bad_offset\":%llu,\"first_bad_pass\":%u,"
+           "\"first_bad_xor\":\"%s\",",
+           static_cast<unsigned long long>(r.first_bad_offset), r.first_bad_pass,
+           hex128(r.first_bad_xor).c_str());
+  else
+    printf("\"first_bad_offset\":null,\"first_bad_pass\":null,"
+           "\"first_bad_xor\":null,");
+  printf("\"write_gbs\":%.3f,\"read_gbs\":%.3f,\"write_gbs_plain\":%.3f,"
+         "\"write_gbs_nontemporal\":%.3f,\"store_variant\":\"%s\",",
+         r.write_gbs, r.read_gbs, r.write_gbs_plain, r.write_gbs_nontemporal,
+         r.store_variant);
+  printf("\"bandwidth\":\"%s\",\"copy_gbs\":%.3f,\"min_copy_gbs\":%.3f,"
+         "\"cache_resident\":%s,",
+         r.bandwidth, r.copy_gbs, o.min_copy_gbs,
+         o.bytes < kCacheResidentBelow ? "true" : "false");
+  printf("\"mfma\":\"%s\",\"mfma_waves\":%ld,\"mfma_bad_waves\":%ld,"
+         "\"mfma_first_bad_wave\":%ld,",
+         r.mfma, r.mfma_waves, r.mfma_bad_waves, r.mfma_first_bad_wave);
+  if (o.dump_pattern) {
+    printf("\"pattern_dump\":[");
+    for (size_t i = 0; i < r.pattern_dump.size(); ++i)
+      printf("%s\"%s\"", i ? "," : "", r.pattern_dump[i].c_str());
+    printf("],");
+  }
+  printf("\"wall_s\":%.4f}\n", wall_s);
+  fflush(stdout);
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  const auto t0 = std::chrono::steady_clock::now();
+  Options o;
+  if (int rc = parse_args(argc, argv, &o)) return rc;
+
+  Report rep;
+  try {
+    if (o.cpu) {
+      CpuBackend be(o);
+      if (be.mem == nullptr) {
+        fprintf(stderr, "gpucheck: cannot allocate %zu bytes\n", o.bytes);
+        return 2;
+      }
+      run_hbm(be, o, &rep);
+    } else {
+      int count = 0;
+      HIP_CHECK(hipGetDeviceCount(&count));
+      if (count < 1) throw HipError{"no visible GPU"};
+      HIP_CHECK(hipSetDevice(0));
+      hipDeviceProp_t prop;
+      HIP_CHECK(hipGetDeviceProperties(&prop, 0));
+      rep.device = std::string(prop.name) + " " + prop.gcnArchName;
+      rep.compute_units = prop.multiProcessorCount;
+      {
+        GpuBackend be(o);
+        run_hbm(be, o, &rep);
+        run_copy(be, o, &rep);
+      }
+      run_mfma(o, prop.multiProcessorCount, &rep);
+    }
+  } catch (const HipError& e) {
+    fprintf(stderr, "gpucheck: %s\n", e.what.c_str());
+    printf("{\"tool\":\"gpucheck\",\"ok\":false,\"exit_code\":11,"
+           "\"failed_stages\":[\"hip\"],\"error\":\"%s\"}\n",
+           json_escape(e.what).c_str());
+    fflush(stdout);
+    return 11;
+  }
+
+  int code = 0;
+  if (rep.mismatch_vectors != 0) code = 20;
+  else if (!strcmp(rep.mfma, "fail")) code = 21;
+  else if (!strcmp(rep.bandwidth, "fail")) code = 22;
+  const double wall_s =
+      std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  print_report(o, rep, code, wall_s);
+  return code;
+}

@@ -98,6 +98,9 @@ class Provider:
         # the reference gets from the virtual-kubelet library's recorder
         # (main.go:172-177).
         self.recorder = None
+        # Optional DiagnosticsManager (set by app.build_stack); drives the
+        # start-up and periodic GPU self-tests when configured.
+        self.diagnostics = None
         self.meminfo_reader = None  # injectable memory.available source
         self._port_rechecks: Dict[str, int] = {}
         self._eviction = None
@@ -131,6 +134,14 @@ class Provider:
                 adopt()
             except Exception:
                 log.exception("instance adoption failed")
+        if self.diagnostics is not None and self.config.gpu_check_on_start:
+            # Before the node controller reports capacity: a GPU that fails
+            # here is never counted allocatable. Adopted pods keep their
+            # GPUs (occupied GPUs are skipped).
+            try:
+                self.diagnostics.check_all_idle()
+            except Exception:
+                log.exception("start-up gpu self-test failed to run")
         self.check_backend_health()
         self.cleanup_stuck_terminating_pods()
         self.registrar.register()  # optional, non-fatal (unlike kubelet.go:369)
@@ -144,6 +155,11 @@ class Provider:
             Ticker(self.config.pending_retry_interval_s, self.process_pending_pods,
                    "pending-pods").start(),
         ]
+        if self.diagnostics is not None and self.config.gpu_check_interval_s > 0:
+            # wake often enough to honour the interval, never busier than 1 Hz
+            self._tickers.append(
+                Ticker(max(1.0, min(60.0, self.config.gpu_check_interval_s / 4)),
+                       self.diagnostics.periodic, "gpu-check").start())
         if self.config.eviction_memory_threshold_mb > 0:
             from .eviction import EvictionManager
 
@@ -1341,6 +1357,7 @@ class Provider:
                     "busyPercent": s.gpu.busy_percent,
                     "temperatureCelsius": (s.gpu.temperature_mc / 1000.0
                                            if s.gpu.temperature_mc >= 0 else None),
+                    "lastCheck": s.gpu.diag_last,
                 }
                 for s in self.ledger.snapshot()
             ]

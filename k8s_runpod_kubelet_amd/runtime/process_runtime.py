@@ -467,6 +467,12 @@ class ProcessRuntime(Runtime):
                 argv += ["--listen-port", str(port)]
         elif argv[0] in ("podworker", "amdvk-podworker"):
             argv[0] = self.podworker_path()
+        elif argv[0] in ("gpucheck", "amdvk-gpucheck"):
+            # the GPU self-test as a pod (a Job): its exit code is the
+            # container's (0 pass, 20 HBM, 21 MFMA, 22 bandwidth)
+            from ..ops import gpucheck_binary
+
+            argv[0] = gpucheck_binary()
         if image is None:
             needs_fast_path = (uid >= 0 or gid >= 0 or self.pod_namespaces)
             if needs_fast_path and "/" not in argv[0]:

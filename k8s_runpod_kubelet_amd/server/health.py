@@ -7,6 +7,7 @@ thread-dump debug endpoint the reference lacks (SURVEY §5.1/5.5 gaps)."""
 
 from __future__ import annotations
 
+import json
 import logging
 import sys
 import threading
@@ -16,6 +17,7 @@ from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from ..utils.httpserver import QuietThreadingHTTPServer
 from typing import Callable, Optional
 
+from ..gpu.diagnostics import GpuBusyError, UnknownGpuError
 from . import metrics
 
 log = logging.getLogger("server.health")
@@ -23,7 +25,7 @@ log = logging.getLogger("server.health")
 
 class HealthServer:
     def __init__(self, address: str, ready_fn: Optional[Callable[[], None]] = None,
-                 ledger=None, admin_token: str = ""):
+                 ledger=None, admin_token: str = "", diagnostics=None):
         host, _, port = address.rpartition(":")
         self.host = host or "0.0.0.0"
         self.port = int(port)
@@ -35,6 +37,8 @@ class HealthServer:
         # health server binds 0.0.0.0 by default for probes — without this
         # gate any network peer could cordon every GPU.
         self.admin_token = admin_token
+        # DiagnosticsManager: enables POST /gpucheck/<idx> and GET /gpucheck
+        self.diagnostics = diagnostics
         self._alive = True
         self._server: Optional[ThreadingHTTPServer] = None
         self._thread: Optional[threading.Thread] = None
@@ -89,6 +93,17 @@ class HealthServer:
                                 for line in traceback.format_stack(frame)
                             )
                     self._respond(200, "\n".join(lines).encode())
+                elif (self.path.rstrip("/") == "/gpucheck"
+                        and outer.diagnostics is not None):
+                    # Last self-test result per GPU; gated like the other
+                    # admin endpoints (results carry device details).
+                    if not self._admin_authorized():
+                        self._respond(403, b"admin endpoint: loopback or "
+                                           b"bearer token required")
+                        return
+                    body = json.dumps(outer.diagnostics.last_results(),
+                                      sort_keys=True).encode()
+                    self._respond(200, body, "application/json")
                 else:
                     self._respond(404, b"not found")
 
@@ -125,6 +140,29 @@ class HealthServer:
                     log.info("gpu cordon state changed",
                              extra={"gpu": idx, "cordoned": cordoned})
                     self._respond(200, b"ok")
+                elif (len(parts) == 2 and parts[0] == "gpucheck"
+                        and outer.diagnostics is not None):
+                    # Operator-triggered self-test: POST /gpucheck/<idx>
+                    # runs gpucheck on an idle GPU and returns its result.
+                    if not self._admin_authorized():
+                        self._respond(403, b"admin endpoint: loopback or "
+                                           b"bearer token required")
+                        return
+                    try:
+                        idx = int(parts[1])
+                    except ValueError:
+                        self._respond(400, b"bad gpu index")
+                        return
+                    try:
+                        result = outer.diagnostics.check(idx, operator=True)
+                    except UnknownGpuError:
+                        self._respond(404, f"no GPU {idx}".encode())
+                        return
+                    except GpuBusyError as exc:
+                        self._respond(409, str(exc).encode())
+                        return
+                    body = json.dumps(result.to_dict(), sort_keys=True).encode()
+                    self._respond(200, body, "application/json")
                 else:
                     self._respond(404, b"not found")
 

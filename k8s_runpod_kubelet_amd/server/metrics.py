@@ -86,5 +86,39 @@ def observe_gpus(states: List) -> None:
         gpu_schedulable.labels(label).set(1 if state.schedulable else 0)
 
 
+# Active self-test (gpu/diagnostics.py). Series appear once a GPU has been
+# checked; with the feature off there are none.
+gpu_check_ok = Gauge("amdvk_gpu_check_ok",
+                     "1 if the GPU's self-test verdict is good",
+                     ["gpu"], registry=registry)
+gpu_check_copy_gbs = Gauge("amdvk_gpu_check_copy_gbs",
+                           "Copy bandwidth of the last self-test (GB/s)",
+                           ["gpu"], registry=registry)
+gpu_check_read_gbs = Gauge("amdvk_gpu_check_read_gbs",
+                           "Verify-read bandwidth of the last self-test (GB/s)",
+                           ["gpu"], registry=registry)
+gpu_check_write_gbs = Gauge("amdvk_gpu_check_write_gbs",
+                            "Fill-write bandwidth of the last self-test (GB/s)",
+                            ["gpu"], registry=registry)
+gpu_check_timestamp = Gauge("amdvk_gpu_check_timestamp_seconds",
+                            "Unix time of the last self-test",
+                            ["gpu"], registry=registry)
+gpu_check_failures = Counter("amdvk_gpu_check_failures_total",
+                             "Failed self-tests by failing stage",
+                             ["gpu", "stage"], registry=registry)
+
+
+def observe_gpu_check(index: int, result, verdict_ok: bool) -> None:
+    label = str(index)
+    gpu_check_ok.labels(label).set(1 if verdict_ok else 0)
+    gpu_check_timestamp.labels(label).set(result.timestamp)
+    for gauge, key in ((gpu_check_copy_gbs, "copy_gbs"),
+                       (gpu_check_read_gbs, "read_gbs"),
+                       (gpu_check_write_gbs, "write_gbs")):
+        value = result.data.get(key)
+        if isinstance(value, (int, float)):
+            gauge.labels(label).set(value)
+
+
 def render() -> bytes:
     return generate_latest(registry)

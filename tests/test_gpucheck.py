@@ -1,0 +1,674 @@
+"""Active GPU self-test — everything that needs no GPU: the gpucheck binary
+in ``--cpu`` mode (CLI, JSON, exit codes, tail handling, 64-bit indices,
+mismatch localisation), the child-process runner against stub executables,
+the DiagnosticsManager gating placement, and the operator surfaces."""
+
+import json
+import os
+import stat
+import subprocess
+import threading
+import time
+import urllib.error
+import urllib.request
+
+import pytest
+
+from k8s_runpod_kubelet_amd.config import Config
+from k8s_runpod_kubelet_amd.gpu.binder import Binder, BindRequest, PlacementError
+from k8s_runpod_kubelet_amd.gpu.diagnostics import (
+    DiagnosticsManager, GpuBusyError, GpuCheckResult, UnknownGpuError,
+    run_gpucheck)
+from tests.conftest import wait_until
+
+
+# ------------------------------------------------------------------ binary
+
+@pytest.fixture(scope="module")
+def gpucheck():
+    from k8s_runpod_kubelet_amd.ops import build
+
+    path = build.build_gpucheck()
+    assert path == build.gpucheck_path() and path.exists()
+    assert os.access(path, os.X_OK)
+    return str(path)
+
+
+def run_cpu(binary, *args):
+    proc = subprocess.run([binary, "--cpu", *map(str, args)],
+                          capture_output=True, text=True, timeout=60)
+    lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
+    return proc.returncode, (json.loads(lines[-1]) if lines else None)
+
+
+def test_builds_through_ops_build(gpucheck):
+    from k8s_runpod_kubelet_amd.ops import build, gpucheck_binary
+
+    assert gpucheck_binary() == gpucheck
+    # the content stamp makes a second build a no-op
+    before = os.stat(gpucheck).st_mtime_ns
+    build.build_gpucheck()
+    assert os.stat(gpucheck).st_mtime_ns == before
+
+
+def test_cpu_clean_region_with_tail(gpucheck):
+    rc, out = run_cpu(gpucheck, "--bytes", 4112)
+    assert rc == 0
+    assert out["ok"] is True and out["mode"] == "cpu"
+    assert out["bytes"] == 4112 and out["vectors"] == 257
+    assert out["mismatch_vectors"] == 0
+    assert out["first_bad_offset"] is None
+    # no GPU in --cpu mode: those stages are reported, not silently dropped
+    assert out["mfma"] == "skipped" and out["bandwidth"] == "skipped"
+
+
+def test_cpu_injected_flip_is_localised(gpucheck):
+    rc, out = run_cpu(gpucheck, "--bytes", 4112, "--inject-flip", "4100:3")
+    assert rc == 20
+    assert out["ok"] is False and out["failed_stages"] == ["hbm"]
+    assert out["mismatch_vectors"] == 1
+    assert out["first_bad_offset"] == 4096
+    assert len(out["first_bad_xor"]) == 32
+    assert int(out["first_bad_xor"], 16) == 1 << (8 * (4100 - 4096) + 3)
+
+
+@pytest.mark.parametrize("nbytes", [16, 31])
+def test_cpu_single_vector_regions(gpucheck, nbytes):
+    rc, out = run_cpu(gpucheck, "--bytes", nbytes)
+    assert rc == 0
+    assert out["bytes"] == 16 and out["vectors"] == 1
+    # ...and that one vector really is tested
+    rc, out = run_cpu(gpucheck, "--bytes", nbytes, "--inject-flip", "15:7")
+    assert rc == 20
+    assert out["mismatch_vectors"] == 1 and out["first_bad_offset"] == 0
+    assert int(out["first_bad_xor"], 16) == 1 << 127
+
+
+def test_cpu_odd_pass_is_complement(gpucheck):
+    """A flip injected after the pass-0 fill is seen by pass 0 only: pass 1
+    rewrites every cell with the complement and verifies clean."""
+    rc, out = run_cpu(gpucheck, "--bytes", 256, "--passes", 3,
+                      "--inject-flip", "0:0")
+    assert rc == 20
+    assert out["mismatch_vectors"] == 1 and out["first_bad_pass"] == 0
+
+
+def test_cpu_base_index_is_64_bit(gpucheck):
+    base = 4294967295
+    rc, hi = run_cpu(gpucheck, "--bytes", 64, "--base-index", base,
+                     "--dump-pattern")
+    assert rc == 0 and hi["mismatch_vectors"] == 0
+    # Vector 1 has logical index 2**32. Its 32-bit-truncated twin is logical
+    # index 0 (vector 1 of a run based at 4294967295 - 2**32 = -1), which is
+    # vector 0 of a base-index-0 run.
+    rc, zero = run_cpu(gpucheck, "--bytes", 64, "--base-index", 0,
+                       "--dump-pattern")
+    assert rc == 0
+    assert len(hi["pattern_dump"]) == 4
+    assert hi["pattern_dump"][1] != zero["pattern_dump"][0]
+    # vector 0 of the high run is logical index 2**32-1, which a 32-bit
+    # index would also reach: both runs agree there.
+    rc, wrap = run_cpu(gpucheck, "--bytes", 64, "--base-index", base - 1,
+                       "--dump-pattern")
+    assert wrap["pattern_dump"][1] == hi["pattern_dump"][0]
+    assert len(set(hi["pattern_dump"])) == 4
+
+
+@pytest.mark.parametrize("args", [
+    ["--bogus"],
+    ["--bytes"],
+    ["--bytes", "12x"],
+    ["--passes", "0"],
+    ["--inject-flip", "5"],
+    ["--inject-flip", "0:8"],
+    ["--bytes", "64", "--inject-flip", "64:0"],
+    ["--min-copy-gbs", "-1"],
+    ["--mfma-waves", "0"],
+])
+def test_bad_flags_exit_2(gpucheck, args):
+    proc = subprocess.run([gpucheck, "--cpu", *args], capture_output=True,
+                          text=True, timeout=60)
+    assert proc.returncode == 2
+    assert "usage:" in proc.stderr
+
+
+# ------------------------------------------------------------------ runner
+
+GOOD_JSON = {"tool": "gpucheck", "ok": True, "exit_code": 0,
+             "mismatch_vectors": 0, "copy_gbs": 3210.5, "read_gbs": 2100.25,
+             "write_gbs": 1900.75, "mfma_bad_waves": 0}
+
+
+def write_stub(tmp_path, name, body):
+    path = tmp_path / name
+    path.write_text("#!/bin/sh\n" + body)
+    path.chmod(path.stat().st_mode | stat.S_IXUSR)
+    return str(path)
+
+
+@pytest.fixture
+def inventory(synthetic_ledger):
+    return synthetic_ledger.inventory
+
+
+def test_runner_pass(tmp_path, inventory):
+    stub = write_stub(tmp_path, "good", f"""echo "warming up"
+echo "$ROCR_VISIBLE_DEVICES $HIP_VISIBLE_DEVICES $@" > {tmp_path}/seen
+echo '{json.dumps(GOOD_JSON)}'
+""")
+    os.environ["ROCR_VISIBLE_DEVICES"] = "7"  # inherited scoping is dropped
+    try:
+        res = run_gpucheck(3, inventory, nbytes=4096, timeout_s=10,
+                           extra_args=["--passes", "1"], binary=stub)
+    finally:
+        del os.environ["ROCR_VISIBLE_DEVICES"]
+    assert isinstance(res, GpuCheckResult)
+    assert res.ok and res.reason == "" and res.exit_code == 0 and res.gpu == 3
+    assert res.data["copy_gbs"] == 3210.5
+    assert (tmp_path / "seen").read_text().split() == [
+        "3", "3", "--bytes", "4096", "--passes", "1"]
+    assert res.to_dict()["ok"] is True and res.to_dict()["gpu"] == 3
+
+
+def test_runner_fail_exit_20(tmp_path, inventory):
+    bad = dict(GOOD_JSON, ok=False, exit_code=20, mismatch_vectors=1,
+               first_bad_offset=4096, failed_stages=["hbm"])
+    stub = write_stub(tmp_path, "bad", f"echo '{json.dumps(bad)}'\nexit 20\n")
+    res = run_gpucheck(0, inventory, nbytes=4096, timeout_s=10, binary=stub)
+    assert not res.ok and res.exit_code == 20 and res.reason == "hbm"
+    assert res.data["first_bad_offset"] == 4096
+
+
+def test_runner_timeout_kills_the_group(tmp_path, inventory):
+    stub = write_stub(tmp_path, "slow",
+                      f"echo $$ > {tmp_path}/pid\nsleep 600 &\n"
+                      f"echo $! > {tmp_path}/childpid\nwait\n")
+    t0 = time.monotonic()
+    res = run_gpucheck(0, inventory, nbytes=4096, timeout_s=0.5, binary=stub)
+    assert time.monotonic() - t0 < 10
+    assert not res.ok and res.reason == "timeout"
+    for name in ("pid", "childpid"):
+        pid = int((tmp_path / name).read_text())
+
+        def gone(pid=pid):
+            try:
+                os.kill(pid, 0)
+            except ProcessLookupError:
+                return True
+            # a zombie awaiting its reaper counts as gone
+            with open(f"/proc/{pid}/stat") as fh:
+                return fh.read().rsplit(")", 1)[1].split()[0] == "Z"
+
+        assert wait_until(gone, timeout_s=5), name
+
+
+def test_runner_garbage_and_signal(tmp_path, inventory):
+    stub = write_stub(tmp_path, "garbage", "echo 'not json at all'\n")
+    res = run_gpucheck(0, inventory, nbytes=4096, timeout_s=10, binary=stub)
+    assert not res.ok and res.reason == "bad-output"
+    stub = write_stub(tmp_path, "empty", "exit 0\n")
+    res = run_gpucheck(0, inventory, nbytes=4096, timeout_s=10, binary=stub)
+    assert not res.ok and res.reason == "bad-output"
+    stub = write_stub(tmp_path, "segv", "kill -SEGV $$\n")
+    res = run_gpucheck(0, inventory, nbytes=4096, timeout_s=10, binary=stub)
+    assert not res.ok and res.reason == "signal 11"
+
+
+def test_runner_real_binary_cpu_mode(gpucheck, inventory):
+    res = run_gpucheck(0, inventory, nbytes=4112, timeout_s=30,
+                       extra_args=["--cpu"], binary=gpucheck)
+    assert res.ok and res.data["vectors"] == 257
+    res = run_gpucheck(0, inventory, nbytes=4112, timeout_s=30,
+                       extra_args=["--cpu", "--inject-flip", "4100:3"])
+    assert not res.ok and res.reason == "hbm" and res.exit_code == 20
+
+
+# ----------------------------------------------------------------- manager
+
+class StubRunner:
+    """Stands in for run_gpucheck; records calls and what the ledger looked
+    like while the 'check' was running."""
+
+    def __init__(self, ledger):
+        self.ledger = ledger
+        self.calls = []
+        self.fail = {}          # idx -> (exit_code, reason, data)
+        self.during = []        # (idx, reservation, occupied) per call
+        self.gate = None        # optional threading.Event to block on
+        self.active = 0
+        self.max_active = 0
+        self._lock = threading.Lock()
+
+    def __call__(self, gpu, inventory, *, nbytes, timeout_s, extra_args=()):
+        with self._lock:
+            self.calls.append((gpu, nbytes, timeout_s, tuple(extra_args)))
+            self.active += 1
+            self.max_active = max(self.max_active, self.active)
+        res = self.ledger.get_reservation(f"amdvk-system/gpucheck-{gpu}")
+        self.during.append((gpu, res, self.ledger.states[gpu].occupied))
+        if self.gate is not None:
+            assert self.gate.wait(10)
+        with self._lock:
+            self.active -= 1
+        now = time.time()
+        if gpu in self.fail:
+            code, reason, data = self.fail[gpu]
+            return GpuCheckResult(gpu=gpu, ok=False, exit_code=code,
+                                  reason=reason, data=dict(data),
+                                  duration_s=0.01, timestamp=now)
+        return GpuCheckResult(gpu=gpu, ok=True, exit_code=0,
+                              data=dict(GOOD_JSON), duration_s=0.01,
+                              timestamp=now)
+
+
+HBM_FAIL = (20, "hbm", {"ok": False, "mismatch_vectors": 1,
+                        "first_bad_offset": 4096, "failed_stages": ["hbm"]})
+
+
+class Recorder:
+    def __init__(self):
+        self.events = []
+
+    def event(self, obj, event_type, reason, message):
+        self.events.append((obj, event_type, reason, message))
+
+
+@pytest.fixture
+def manager(synthetic_ledger):
+    cfg = Config(gpu_check_bytes=1 << 20, gpu_check_interval_s=3600.0)
+    runner = StubRunner(synthetic_ledger)
+    rec = Recorder()
+    mgr = DiagnosticsManager(synthetic_ledger, synthetic_ledger.inventory, cfg,
+                             runner=runner, recorder=rec, node_name="node-a")
+    return mgr, runner, rec, synthetic_ledger
+
+
+def test_manager_failed_check_fences_gpu(manager):
+    mgr, runner, rec, ledger = manager
+    runner.fail[2] = HBM_FAIL
+    res = mgr.check(2)
+    assert not res.ok
+    st = ledger.states[2]
+    assert not st.schedulable and st.gpu.healthy and not st.cordoned
+    assert st.gpu.diag_ok is False and st.gpu.diag_reason == "hbm"
+    assert st.gpu.diag_last["first_bad_offset"] == 4096
+    assert ledger.schedulable_count() == 7
+    # the binder never returns it: fill the node one GPU at a time
+    binder = Binder(ledger)
+    picked = []
+    for i in range(7):
+        picked += binder.bind(BindRequest(f"default-p{i}", 1, 0, max_cost=1.0))
+    assert sorted(picked) == [0, 1, 3, 4, 5, 6, 7]
+    with pytest.raises(PlacementError):
+        binder.select(BindRequest("default-p8", 1, 0, max_cost=1.0))
+    # Warning Event on the node with the stage and the offset
+    (obj, etype, reason, message), = rec.events
+    assert obj["kind"] == "Node" and obj["metadata"]["name"] == "node-a"
+    assert etype == "Warning" and reason == "GpuCheckFailed"
+    assert "stage=hbm" in message and "first_bad_offset=4096" in message
+
+
+def test_manager_refuses_occupied_and_unknown(manager):
+    mgr, runner, _, ledger = manager
+    ledger.reserve("default-tenant", [1], 1 << 30)
+    with pytest.raises(GpuBusyError):
+        mgr.check(1)
+    with pytest.raises(UnknownGpuError):
+        mgr.check(99)
+    assert runner.calls == []
+    assert ledger.get_reservation("default-tenant") is not None
+
+
+def test_manager_reservation_held_then_released(manager):
+    mgr, runner, _, ledger = manager
+    before = time.monotonic()
+    res = mgr.check(4)
+    assert res.ok
+    (gpu, held, occupied), = runner.during
+    assert gpu == 4 and occupied
+    assert held is not None and held.gpu_indices == [4]
+    assert held.bytes_per_gpu == 1 << 20
+    assert runner.calls == [(4, 1 << 20, 60.0, ())]
+    # released, with the settle stamp any freed GPU gets
+    assert ledger.get_reservation("amdvk-system/gpucheck-4") is None
+    assert not ledger.states[4].occupied
+    assert ledger.states[4].reserved_bytes == 0
+    assert ledger.states[4].last_freed_at >= before
+    assert ledger.states[4].schedulable
+
+
+def test_manager_binder_cannot_place_during_check(manager):
+    mgr, runner, _, ledger = manager
+    for i in range(7):  # leave only GPU 7 free
+        ledger.reserve(f"default-t{i}", [i], 0)
+    runner.gate = threading.Event()
+    t = threading.Thread(target=mgr.check, args=(7,))
+    t.start()
+    try:
+        assert wait_until(lambda: runner.during, timeout_s=5)
+        with pytest.raises(PlacementError):
+            Binder(ledger).select(BindRequest("default-x", 1, 0, max_cost=1.0))
+        # one check per GPU at a time
+        with pytest.raises(GpuBusyError):
+            mgr.check(7)
+    finally:
+        runner.gate.set()
+        t.join(10)
+    assert Binder(ledger).select(
+        BindRequest("default-x", 1, 0, max_cost=1.0)) == [7]
+
+
+def test_manager_failed_state_survives_refresh_and_rediscovery(manager):
+    mgr, runner, _, ledger = manager
+    runner.fail[5] = HBM_FAIL
+    mgr.check(5)
+    ledger.inventory.refresh_dynamic()
+    ledger.sync_inventory()
+    assert not ledger.states[5].schedulable
+    # a re-discovery hands the ledger brand-new Gpu records
+    ledger.inventory.discover()
+    ledger.sync_inventory()
+    assert ledger.states[5].gpu is ledger.inventory.get(5)
+    assert ledger.states[5].gpu.diag_ok is False
+    assert ledger.states[5].gpu.diag_reason == "hbm"
+    assert not ledger.states[5].schedulable
+    assert ledger.states[4].schedulable
+
+
+def test_manager_only_operator_recheck_clears_failure(manager):
+    mgr, runner, _, ledger = manager
+    runner.fail[6] = HBM_FAIL
+    mgr.check(6)
+    del runner.fail[6]
+    # a passing non-operator check does not clear it, and takes no
+    # reservation (the GPU is unschedulable anyway)
+    runner.during.clear()
+    assert mgr.check(6).ok
+    assert runner.during == [(6, None, False)]
+    assert not ledger.states[6].schedulable
+    assert ledger.states[6].gpu.diag_reason == "hbm"
+    assert mgr.check(6, operator=True).ok
+    assert ledger.states[6].schedulable
+    assert ledger.states[6].gpu.diag_reason == ""
+    assert ledger.states[6].gpu.diag_last["ok"] is True
+
+
+def test_manager_periodic_skips_failed_occupied_and_fresh(manager):
+    mgr, runner, _, ledger = manager
+    runner.fail[0] = HBM_FAIL
+    mgr.check(0)
+    ledger.reserve("default-tenant", [1], 0)
+    ledger.set_cordoned(2, True)
+    mgr.check(3)  # fresh result: younger than the interval
+    runner.calls.clear()
+    results = mgr.periodic()
+    assert sorted(c[0] for c in runner.calls) == [4, 5, 6, 7]
+    assert [r.gpu for r in results] == [4, 5, 6, 7]
+    assert runner.max_active <= 2  # gpu_check_parallel default
+    # nothing is stale any more
+    runner.calls.clear()
+    assert mgr.periodic() == [] and runner.calls == []
+    # interval 0 = off
+    mgr.config.gpu_check_interval_s = 0
+    mgr._last_checked.clear()
+    assert mgr.periodic() == [] and runner.calls == []
+
+
+def test_manager_passes_copy_floor(manager):
+    mgr, runner, _, _ = manager
+    mgr.config.gpu_check_min_copy_gbs = 1500.0
+    mgr.check(0)
+    assert runner.calls[0][3] == ("--min-copy-gbs", "1500.0")
+
+
+# ---------------------------------------------------------------- surfaces
+
+def post(url, headers=None):
+    req = urllib.request.Request(url, method="POST", headers=headers or {})
+    try:
+        with urllib.request.urlopen(req, timeout=10) as resp:
+            return resp.status, resp.read().decode()
+    except urllib.error.HTTPError as exc:
+        return exc.code, exc.read().decode()
+
+
+def get(url, headers=None):
+    req = urllib.request.Request(url, headers=headers or {})
+    try:
+        with urllib.request.urlopen(req, timeout=10) as resp:
+            return resp.status, resp.read().decode()
+    except urllib.error.HTTPError as exc:
+        return exc.code, exc.read().decode()
+
+
+def test_gpucheck_endpoints(manager, fake_kube):
+    from k8s_runpod_kubelet_amd.provider.provider import Provider
+    from k8s_runpod_kubelet_amd.runtime.fake import FakeRuntime
+    from k8s_runpod_kubelet_amd.server.health import HealthServer
+
+    mgr, runner, _, ledger = manager
+    hs = HealthServer("127.0.0.1:0", None, ledger=ledger, diagnostics=mgr)
+    hs.start()
+    base = f"http://127.0.0.1:{hs.port}"
+    try:
+        code, body = get(f"{base}/gpucheck")
+        assert code == 200
+        assert json.loads(body)["3"] == {"ok": True, "reason": "",
+                                         "lastCheck": None}
+        code, body = post(f"{base}/gpucheck/3")
+        assert code == 200
+        out = json.loads(body)
+        assert out["ok"] is True and out["gpu"] == 3
+        assert out["copy_gbs"] == 3210.5
+
+        assert post(f"{base}/gpucheck/99")[0] == 404
+        assert post(f"{base}/gpucheck/x")[0] == 400
+        ledger.reserve("default-tenant", [1], 0)
+        assert post(f"{base}/gpucheck/1")[0] == 409
+
+        runner.fail[2] = HBM_FAIL
+        code, body = post(f"{base}/gpucheck/2")
+        assert code == 200 and json.loads(body)["reason"] == "hbm"
+        assert not ledger.states[2].schedulable
+        # an operator re-check that passes restores it
+        del runner.fail[2]
+        runner.fail[4] = HBM_FAIL
+        post(f"{base}/gpucheck/4")
+        code, body = post(f"{base}/gpucheck/2")
+        assert code == 200 and ledger.states[2].schedulable
+
+        code, body = get(f"{base}/gpucheck")
+        last = json.loads(body)
+        assert last["3"]["ok"] is True and last["3"]["lastCheck"]["gpu"] == 3
+        assert last["4"]["ok"] is False and last["4"]["reason"] == "hbm"
+        assert last["4"]["lastCheck"]["first_bad_offset"] == 4096
+        assert last["0"]["lastCheck"] is None
+
+        code, text = get(f"{base}/metrics")
+        assert code == 200
+        assert 'amdvk_gpu_check_ok{gpu="3"} 1.0' in text
+        assert 'amdvk_gpu_check_ok{gpu="4"} 0.0' in text
+        assert 'amdvk_gpu_check_copy_gbs{gpu="3"} 3210.5' in text
+        assert 'amdvk_gpu_check_read_gbs{gpu="3"} 2100.25' in text
+        assert 'amdvk_gpu_check_write_gbs{gpu="3"} 1900.75' in text
+        assert 'amdvk_gpu_check_timestamp_seconds{gpu="3"}' in text
+        assert ('amdvk_gpu_check_failures_total{gpu="4",stage="hbm"}'
+                in text)
+
+        prov = Provider(fake_kube, Config(notify_interval_s=0),
+                        FakeRuntime(gpu_count=8), ledger=ledger,
+                        inventory=ledger.inventory)
+        gpus = {g["index"]: g for g in prov.get_stats_summary()["gpus"]}
+        assert gpus[3]["lastCheck"]["ok"] is True
+        assert gpus[4]["lastCheck"]["reason"] == "hbm"
+        assert gpus[0]["lastCheck"] is None
+    finally:
+        hs.stop()
+
+
+def test_gpucheck_endpoint_absent_without_manager(synthetic_ledger):
+    from k8s_runpod_kubelet_amd.server.health import HealthServer
+
+    hs = HealthServer("127.0.0.1:0", None, ledger=synthetic_ledger)
+    hs.start()
+    try:
+        base = f"http://127.0.0.1:{hs.port}"
+        assert post(f"{base}/gpucheck/0")[0] == 404
+        assert get(f"{base}/gpucheck")[0] == 404
+    finally:
+        hs.stop()
+
+
+def _nonloopback_ip():
+    import socket
+
+    s = socket.socket(socket.AF_INET, socket.SOCK_DGRAM)
+    try:
+        s.connect(("10.255.255.255", 1))
+        ip = s.getsockname()[0]
+        return None if ip.startswith("127.") else ip
+    except OSError:
+        return None
+    finally:
+        s.close()
+
+
+def test_gpucheck_admin_requires_loopback_or_token(manager):
+    from k8s_runpod_kubelet_amd.server.health import HealthServer
+
+    mgr, runner, _, ledger = manager
+    ip = _nonloopback_ip()
+    if ip is None:
+        pytest.skip("no non-loopback interface")
+    hs = HealthServer("0.0.0.0:0", None, ledger=ledger, admin_token="sekrit",
+                      diagnostics=mgr)
+    hs.start()
+    try:
+        base = f"http://{ip}:{hs.port}"
+        assert post(f"{base}/gpucheck/3")[0] == 403
+        assert post(f"{base}/gpucheck/3",
+                    {"Authorization": "Bearer nope"})[0] == 403
+        assert get(f"{base}/gpucheck")[0] == 403
+        assert runner.calls == []
+        assert post(f"{base}/gpucheck/3",
+                    {"Authorization": "Bearer sekrit"})[0] == 200
+        assert get(f"{base}/gpucheck",
+                   {"Authorization": "Bearer sekrit"})[0] == 200
+        # loopback needs no token
+        assert post(f"http://127.0.0.1:{hs.port}/gpucheck/3")[0] == 200
+        assert [c[0] for c in runner.calls] == [3, 3]
+    finally:
+        hs.stop()
+
+
+# ------------------------------------------------------------- full stack
+
+def _stack(tmp_path, **cfg_kw):
+    from k8s_runpod_kubelet_amd.app import build_stack
+    from k8s_runpod_kubelet_amd.kube.fake import FakeKube
+
+    cfg = Config(state_dir=str(tmp_path), notify_interval_s=0,
+                 gpu_count_override=8, **cfg_kw)
+    stack = build_stack(cfg, client=FakeKube())
+    runner = StubRunner(stack.ledger)
+    stack.diagnostics.runner = runner
+    return stack, runner
+
+
+def test_defaults_never_run_a_check(tmp_path):
+    cfg = Config()
+    assert cfg.gpu_check_on_start is False
+    assert cfg.gpu_check_interval_s == 0
+    assert cfg.gpu_check_bytes == 1 << 30
+    assert cfg.gpu_check_timeout_s == 60
+    assert cfg.gpu_check_min_copy_gbs == 0
+    assert cfg.gpu_check_parallel == 2
+    stack, runner = _stack(tmp_path)
+    stack.start(serve_http=False)
+    try:
+        stack.provider._periodic_reconcile()
+        assert not any(t.name == "gpu-check" for t in stack.provider._tickers)
+        assert stack.diagnostics.periodic() == []
+        assert runner.calls == []
+        assert stack.ledger.schedulable_count() == 8
+    finally:
+        stack.stop()
+
+
+def test_check_on_start_gates_capacity(tmp_path):
+    stack, runner = _stack(tmp_path, gpu_check_on_start=True,
+                           gpu_check_interval_s=3600.0,
+                           gpu_check_bytes=1 << 20)
+    runner.fail[5] = HBM_FAIL
+    stack.start(serve_http=False)
+    try:
+        assert sorted(c[0] for c in runner.calls) == list(range(8))
+        assert any(t.name == "gpu-check" for t in stack.provider._tickers)
+        node = stack.provider.get_node_status()
+        assert node["status"]["capacity"]["amd.com/gpu"] == "8"
+        assert node["status"]["allocatable"]["amd.com/gpu"] == "7"
+        assert not stack.ledger.reservations
+        # the real EventRecorder put a Warning on the node
+        events = [e for e in stack.client.events.objects.values()
+                  if e["reason"] == "GpuCheckFailed"]
+        assert len(events) == 1
+        assert events[0]["type"] == "Warning"
+        assert events[0]["involvedObject"]["kind"] == "Node"
+        assert events[0]["involvedObject"]["name"] == stack.config.node_name
+        assert "stage=hbm" in events[0]["message"]
+        assert "first_bad_offset=4096" in events[0]["message"]
+    finally:
+        stack.stop()
+
+
+def test_cli_flags_reach_config():
+    from k8s_runpod_kubelet_amd.cli import build_parser
+
+    args = build_parser().parse_args([])
+    assert args.gpu_check_on_start is None and args.gpu_check_interval is None
+    args = build_parser().parse_args([
+        "--gpu-check-on-start", "--gpu-check-interval", "6h",
+        "--gpu-check-bytes", "4G", "--gpu-check-timeout", "90s",
+        "--gpu-check-min-copy-gbs", "1500", "--gpu-check-parallel", "3"])
+    assert args.gpu_check_on_start is True
+    assert args.gpu_check_interval == "6h"
+    from k8s_runpod_kubelet_amd.gpu.diagnostics import parse_size
+
+    assert parse_size(args.gpu_check_bytes) == 4 << 30
+    assert parse_size("4096") == 4096 and parse_size("512MiB") == 512 << 20
+
+
+def test_operator_cli_runs_binary(gpucheck, capsys):
+    from k8s_runpod_kubelet_amd.gpu import diagnostics
+
+    code = diagnostics.main(["--gpu", "0", "--bytes", "4112",
+                             "--sysfs-root", "/nonexistent-sysfs",
+                             "--", "--cpu", "--inject-flip", "4100:3"])
+    out = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert code == 20 and out["reason"] == "hbm"
+    assert out["first_bad_offset"] == 4096
+    code = diagnostics.main(["--gpu", "0", "--bytes", "4K",
+                             "--sysfs-root", "/nonexistent-sysfs",
+                             "--", "--cpu"])
+    out = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert code == 0 and out["ok"] is True and out["bytes"] == 4096
+
+
+def test_gpucheck_as_pod_command(gpucheck, process_runtime):
+    from k8s_runpod_kubelet_amd.runtime.types import (
+        ContainerSpec, DeployParams, PodStatus)
+
+    st = process_runtime.deploy(DeployParams(
+        pod_key="default-diag", name="diag", gpu_count=0,
+        containers=[ContainerSpec(
+            name="main", command=["gpucheck", "--cpu", "--bytes", "4096"])],
+    ))
+
+    def exited():
+        s = process_runtime.get_detailed_status(st.id)
+        return s if s.desired_status == PodStatus.EXITED else None
+
+    s = wait_until(exited, timeout_s=30)
+    assert s is not None, process_runtime.get_logs(st.id)
+    assert s.exit_code == 0, process_runtime.get_logs(st.id)
+    assert '"mismatch_vectors":0' in process_runtime.get_logs(st.id)
