@@ -1,7 +1,10 @@
 # Two-stage build (reference Dockerfile:1-22 pattern: builder -> minimal
-# runtime). The builder compiles the native probe/launcher extension and the
-# gfx950 podworker with hipcc; the runtime stage carries only ROCm runtime
-# libs + python.
+# runtime). The builder compiles the native probe/launcher extension with
+# g++, the podworker's gfx950 code object and gpucheck with hipcc, and the
+# podworker host program with g++ against libhsa-runtime64 (RUNPATH to the
+# ROCm lib directory, which the runtime image has at the same place); the
+# runtime stage carries only ROCm runtime libs + python. The podworker needs
+# ROCr alone there; gpucheck still needs the HIP runtime.
 FROM rocm/dev-ubuntu-22.04:7.2 AS builder
 RUN apt-get update && apt-get install -y --no-install-recommends \
         python3 python3-pip g++ && rm -rf /var/lib/apt/lists/*
