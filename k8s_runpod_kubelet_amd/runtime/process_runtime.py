@@ -33,7 +33,6 @@ kubelet.go:1380-1535) without double-binding GPUs.
 
 from __future__ import annotations
 
-import dataclasses
 import json
 import logging
 import os
@@ -46,6 +45,7 @@ from typing import Callable, Dict, List, Optional
 
 from ..gpu.binder import Binder, BindRequest, PlacementError, device_env
 from ..gpu.ledger import Ledger
+from . import journal, procfs
 from .base import Runtime
 from .types import (
     ContainerRuntimeInfo,
@@ -56,8 +56,6 @@ from .types import (
 )
 
 log = logging.getLogger("runtime.process")
-
-TERM_GRACE_S = 10.0
 
 
 class ProcessRuntime(Runtime):
@@ -207,11 +205,9 @@ class ProcessRuntime(Runtime):
         with self._lock:
             self._instances[instance_id] = inst
             if params.active_deadline_s > 0:
-                t = threading.Timer(params.active_deadline_s,
-                                    self._deadline_exceeded, args=(instance_id,))
-                t.daemon = True
-                self._deadline_timers[instance_id] = t
-                t.start()
+                self._arm_timer(self._deadline_timers, instance_id,
+                                params.active_deadline_s,
+                                self._deadline_exceeded, instance_id)
         self._persist(inst)
         log.info(
             "deployed instance",
@@ -383,6 +379,34 @@ class ProcessRuntime(Runtime):
                 paths.append(f"/dev/dri/renderD{gpu.render_minor}")
         return [p for p in paths if os.path.exists(p)]
 
+    def _pod_env(self, inst: Instance, cspec=None,
+                 base: Optional[Dict[str, str]] = None) -> Dict[str, str]:
+        """`base` (default: the kubelet's own environment), the pod-level
+        env, the pod's GPU scoping — authoritative over whatever scoping
+        `base` carried — and, when given, the container's env."""
+        env = dict(os.environ if base is None else base)
+        env.update(inst.params.env)
+        env.update(device_env(inst.gpu_indices, self.binder.ledger.inventory))
+        if cspec is not None:
+            env.update(cspec.env)
+        return env
+
+    def _prepare_rootfs(self, inst: Instance, cspec, image, working_dir: str,
+                        argv0: str, **prepare_kw) -> tuple:
+        """Prepare the container's rootfs from `image`; returns (argv0
+        resolved inside it, rootfs, chroot_only, mounts) for the launcher."""
+        params = inst.params
+        prepared = self._rootfs_mgr.prepare(
+            inst.id, cspec.name, image,
+            params.hostname or params.name,
+            gpu_device_paths=self._gpu_device_paths(inst),
+            working_dir=working_dir,
+            volume_binds=self._binds_for(inst, cspec),
+            host_aliases=params.host_aliases,
+            resolv_conf=params.resolv_conf, **prepare_kw)
+        return (self._rootfs_mgr.resolve_argv0(image, prepared, argv0),
+                prepared.rootfs, prepared.chroot_only, prepared.mounts)
+
     def _launch_one(self, inst: Instance, cspec, into: List) -> float:
         """Spawn one container of the pod into `into` (inst.containers or
         inst.init_containers); returns the native posix_spawnp/clone3 time in
@@ -396,19 +420,13 @@ class ProcessRuntime(Runtime):
         if image is not None:
             # container env starts from the IMAGE config, not the kubelet's
             # environment — host env must not leak into containers
-            base_env: Dict[str, str] = {}
-            for e in image.config.env:
-                k, _, v = e.partition("=")
-                base_env[k] = v
+            env = self._pod_env(inst, base=dict(
+                e.partition("=")[::2] for e in image.config.env))
         else:
-            base_env = dict(os.environ)
-        # Drop our own GPU scoping so the pod's binding is authoritative.
-        base_env.pop("ROCR_VISIBLE_DEVICES", None)
-        base_env.pop("HIP_VISIBLE_DEVICES", None)
-        base_env.update(params.env)
-        base_env.update(device_env(inst.gpu_indices, self.binder.ledger.inventory))
-        base_env["AMDVK_INSTANCE_ID"] = inst.id
-        base_env["AMDVK_POD_KEY"] = params.pod_key
+            env = self._pod_env(inst)
+        env["AMDVK_INSTANCE_ID"] = inst.id
+        env["AMDVK_POD_KEY"] = params.pod_key
+        env.update(cspec.env)
 
         argv = list(cspec.command) + list(cspec.args)
         uid, gid = cspec.run_as_uid, cspec.run_as_gid
@@ -433,20 +451,9 @@ class ProcessRuntime(Runtime):
                 # runs both inside the container), and restarts/adoption
                 # keep it (it is persisted with the spec)
                 cspec.run_as_uid, cspec.run_as_gid = uid, gid
-            prepared = self._rootfs_mgr.prepare(
-                inst.id, cspec.name, image,
-                params.hostname or params.name,
-                gpu_device_paths=self._gpu_device_paths(inst),
-                working_dir=working_dir,
-                volume_binds=self._binds_for(inst, cspec),
-                host_aliases=params.host_aliases,
-                read_only=cspec.read_only_root_fs,
-                resolv_conf=params.resolv_conf)
-            argv[0] = self._rootfs_mgr.resolve_argv0(image, prepared,
-                                                     argv[0])
-            rootfs = prepared.rootfs
-            chroot_only = prepared.chroot_only
-            mounts = prepared.mounts
+            argv[0], rootfs, chroot_only, mounts = self._prepare_rootfs(
+                inst, cspec, image, working_dir, argv[0],
+                read_only=cspec.read_only_root_fs)
         elif not argv:
             if (self._rootfs_mgr is not None and cspec.image
                     and not cspec.image.startswith("amdvk/")):
@@ -475,12 +482,10 @@ class ProcessRuntime(Runtime):
             argv[0] = gpucheck_binary()
         if image is None:
             needs_fast_path = (uid >= 0 or gid >= 0 or self.pod_namespaces)
-            if needs_fast_path and "/" not in argv[0]:
+            if needs_fast_path:
                 # Credential dropping / namespaces happen on the execve fast
                 # path, which does no PATH search — resolve here instead.
-                resolved = shutil.which(argv[0])
-                if resolved:
-                    argv[0] = resolved
+                argv[0] = procfs.resolve_argv0(argv[0])
 
         if cspec.run_as_non_root and uid <= 0:
             # securityContext.runAsNonRoot: k8s refuses to start a
@@ -492,8 +497,6 @@ class ProcessRuntime(Runtime):
                 f"{'root' if uid == 0 else 'the kubelet user (root)'}"
                 " — set runAsUser or an image USER")
 
-        env = dict(base_env)
-        env.update(cspec.env)
         envp = [f"{k}={v}" for k, v in env.items()]
         stdout_path = str(self.logs_dir / f"{inst.id}-{cspec.name}.log")
 
@@ -517,24 +520,14 @@ class ProcessRuntime(Runtime):
                 raise
             # mountns mode failed on this host (overlayfs/caps): downgrade
             # to the chroot mode once, then retry this launch with a
-            # freshly prepared copied rootfs.
+            # freshly prepared copied rootfs (prepared without read_only;
+            # argv[0] re-derived from the spec or the image entrypoint).
             log.warning("mountns image launch failed; retrying in chroot "
                         "mode", extra={"err": str(exc)})
             self._rootfs_mgr.downgrade_to_chroot()
-            prepared = self._rootfs_mgr.prepare(
-                inst.id, cspec.name, image,
-                params.hostname or params.name,
-                gpu_device_paths=self._gpu_device_paths(inst),
-                working_dir=working_dir,
-                volume_binds=self._binds_for(inst, cspec),
-                host_aliases=params.host_aliases,
-                resolv_conf=params.resolv_conf)
-            argv[0] = self._rootfs_mgr.resolve_argv0(
-                image, prepared, (cspec.command or image.config.entrypoint
-                                  or argv)[0])
-            rootfs = prepared.rootfs
-            chroot_only = prepared.chroot_only
-            mounts = prepared.mounts
+            argv[0], rootfs, chroot_only, mounts = self._prepare_rootfs(
+                inst, cspec, image, working_dir,
+                (cspec.command or image.config.entrypoint or argv)[0])
             pid, pidfd, ready_fd, spawn_s, cgroup_s = do_launch()
         if image is not None:
             inst.image_mode = "chroot" if chroot_only else "mountns"
@@ -805,14 +798,27 @@ class ProcessRuntime(Runtime):
         delay = min(60.0, 2.0 ** cinfo.crash_streak)
         cinfo.crash_streak += 1
         cinfo.backoff_until = time.time() + delay
-        timer = threading.Timer(
-            delay, self._restart_container, args=(inst.id, cinfo.name))
-        timer.daemon = True
-        self._restart_timers[(inst.id, cinfo.name)] = timer
-        timer.start()
+        self._arm_timer(self._restart_timers, (inst.id, cinfo.name), delay,
+                        self._restart_container, inst.id, cinfo.name)
         log.info("container restart scheduled",
                  extra={"instance": inst.id, "container": cinfo.name,
                         "delay_s": delay, "restarts": cinfo.restart_count})
+
+    @staticmethod
+    def _arm_timer(timers: dict, key, delay: float, fn, *args) -> None:
+        """Start a daemon timer and file it under `key` in one of
+        _kill_timers / _restart_timers / _deadline_timers."""
+        timer = threading.Timer(delay, fn, args=args)
+        timer.daemon = True
+        timers[key] = timer
+        timer.start()
+
+    def _cancel_restarts(self, instance_id: str) -> None:
+        """Cancel the instance's pending restartPolicy backoff timers."""
+        for key, timer in list(self._restart_timers.items()):
+            if key[0] == instance_id:
+                timer.cancel()
+                self._restart_timers.pop(key, None)
 
     def _restart_container(self, instance_id: str, name: str) -> None:
         # Entire transition under the runtime lock: must not interleave with
@@ -909,10 +915,7 @@ class ProcessRuntime(Runtime):
                         extra={"instance": instance_id, "pod": inst.pod_key})
             inst.deadline_exceeded = True
             inst.last_error = "DeadlineExceeded"
-            for (iid, cname), t in list(self._restart_timers.items()):
-                if iid == instance_id:
-                    t.cancel()
-                    self._restart_timers.pop((iid, cname), None)
+            self._cancel_restarts(instance_id)
             live = False
             for c in list(inst.containers) + list(inst.init_containers):
                 c.backoff_until = 0
@@ -936,10 +939,7 @@ class ProcessRuntime(Runtime):
         dtimer = self._deadline_timers.pop(inst.id, None)
         if dtimer:
             dtimer.cancel()
-        for (iid, cname), t in list(self._restart_timers.items()):
-            if iid == inst.id:
-                t.cancel()
-                self._restart_timers.pop((iid, cname), None)
+        self._cancel_restarts(inst.id)
         for c in inst.ephemeral_containers:
             if c.exit_code is None and c.pid > 0:
                 self._native.signal_process(c.pid, 9, True)
@@ -949,17 +949,16 @@ class ProcessRuntime(Runtime):
         self._release_cgroup(inst.cgroup_dir)
         inst.cgroup_dir = ""
 
-    def _run_hook(self, inst: Instance, cspec, spec) -> bool:
-        """Execute one lifecycle hook (postStart/preStop) confined like an
-        exec probe: container credentials, cgroup, and (image pods) its
-        rootfs."""
+    def _run_handler(self, inst: Instance, cspec, spec) -> bool:
+        """Execute one probe or lifecycle-hook (postStart/preStop) handler
+        of a container. An exec handler is confined like the container
+        itself: same cgroup (device filter included), the container's
+        runAsUser/runAsGroup credentials and env, and — for image pods —
+        the container's rootfs."""
         from .probes import run_probe
 
-        env = dict(os.environ)
-        env.update(inst.params.env)
-        env.update(device_env(inst.gpu_indices,
-                              self.binder.ledger.inventory))
-        env.update(cspec.env)
+        if spec.kind != "exec":
+            return run_probe(spec, {})
         setns_pid, rootfs = self._container_entry(inst, cspec)
 
         def runner(command, penv, timeout_s):
@@ -968,14 +967,32 @@ class ProcessRuntime(Runtime):
                 cspec.run_as_uid, cspec.run_as_gid, timeout_s,
                 setns_pid=setns_pid, rootfs=rootfs)
 
-        return run_probe(spec, env, exec_runner=runner)
+        # (starts from the kubelet's environment even for image pods, and
+        # carries no AMDVK_* — unlike the container's own launch env)
+        return run_probe(spec, self._pod_env(inst, cspec),
+                         exec_runner=runner)
+
+    def _tick_probe(self, inst: Instance, cspec, cinfo, kind: str, now):
+        """Run the container's `kind` probe if it is due and fold the
+        attempt into its state. Returns (thresholded outcome, state);
+        the outcome is None when not due or still undecided."""
+        from .probes import ProbeState, advance
+
+        spec = getattr(cspec, kind)
+        st = self._probe_states.setdefault((inst.id, cspec.name, kind),
+                                           ProbeState())
+        if (now - cinfo.started_at < spec.initial_delay_s
+                or now - st.last_run < spec.period_s):
+            return None, st
+        st.last_run = now
+        return advance(st, spec, self._run_handler(inst, cspec, spec)), st
 
     def _post_start_hook(self, inst: Instance, cspec, pid: int) -> None:
         """k8s postStart: runs right after the container starts; failure
         kills the container into the restartPolicy machinery."""
         ok = False
         try:
-            ok = self._run_hook(inst, cspec, cspec.post_start)
+            ok = self._run_handler(inst, cspec, cspec.post_start)
         except Exception:
             log.exception("postStart hook error")
         if ok:
@@ -999,7 +1016,7 @@ class ProcessRuntime(Runtime):
             if cinfo.exit_code is not None:
                 continue
             try:
-                self._run_hook(inst, cspec, cspec.pre_stop)
+                self._run_handler(inst, cspec, cspec.pre_stop)
             except Exception:
                 log.exception("preStop hook error")
         with self._lock:
@@ -1010,8 +1027,6 @@ class ProcessRuntime(Runtime):
         """One probe-scheduler tick: run due liveness/readiness probes on
         RUNNING containers (see runtime/probes.py; the reference has no
         probe support at all)."""
-        from .probes import ProbeState, advance, run_probe
-
         now = time.time()
         with self._lock:
             insts = [i for i in self._instances.values()
@@ -1025,39 +1040,14 @@ class ProcessRuntime(Runtime):
                 cinfo = by_name.get(cspec.name)
                 if cinfo is None or cinfo.exit_code is not None:
                     continue
-                env = None
                 if cspec.startup is not None:
-                    skey = (inst.id, cspec.name, "startup")
-                    sst = self._probe_states.setdefault(skey, ProbeState())
-                    if sst.result is not True:
+                    sst = self._probe_states.get(
+                        (inst.id, cspec.name, "startup"))
+                    if sst is None or sst.result is not True:
                         # startup owns the container until it passes
                         # (k8s: not Started yet -> no liveness/readiness)
-                        spec = cspec.startup
-                        if now - cinfo.started_at < spec.initial_delay_s:
-                            continue
-                        if now - sst.last_run < spec.period_s:
-                            continue
-                        sst.last_run = now
-                        if spec.kind == "exec":
-                            env = dict(os.environ)
-                            env.update(inst.params.env)
-                            env.update(device_env(
-                                inst.gpu_indices,
-                                self.binder.ledger.inventory))
-                            env.update(cspec.env)
-                            cg = inst.cgroup_dir
-                            uid, gid = cspec.run_as_uid, cspec.run_as_gid
-                            sp, rf = self._container_entry(inst, cspec)
-
-                            def srunner(command, penv, timeout_s, _cg=cg,
-                                        _uid=uid, _gid=gid, _sp=sp, _rf=rf):
-                                return self._run_confined(
-                                    command, penv, _cg, _uid, _gid,
-                                    timeout_s, setns_pid=_sp, rootfs=_rf)
-                        else:
-                            srunner = None
-                        ok = run_probe(spec, env or {}, exec_runner=srunner)
-                        outcome = advance(sst, spec, ok)
+                        outcome, sst = self._tick_probe(
+                            inst, cspec, cinfo, "startup", now)
                         if outcome is False:
                             log.warning(
                                 "startup probe failed; killing container",
@@ -1074,42 +1064,11 @@ class ProcessRuntime(Runtime):
                                 self._persist(inst)
                                 self._notify(inst.id)
                         continue
-                for kind, spec in (("liveness", cspec.liveness),
-                                   ("readiness", cspec.readiness)):
-                    if spec is None:
+                for kind in ("liveness", "readiness"):
+                    if getattr(cspec, kind) is None:
                         continue
-                    key = (inst.id, cspec.name, kind)
-                    st = self._probe_states.setdefault(key, ProbeState())
-                    if now - cinfo.started_at < spec.initial_delay_s:
-                        continue
-                    if now - st.last_run < spec.period_s:
-                        continue
-                    st.last_run = now
-                    exec_runner = None
-                    if spec.kind == "exec":
-                        if env is None:
-                            env = dict(os.environ)
-                            env.update(inst.params.env)
-                            env.update(device_env(inst.gpu_indices,
-                                                  self.binder.ledger.inventory))
-                            env.update(cspec.env)
-                        # confine the probe like the container itself:
-                        # same cgroup (device filter included), the
-                        # container's runAsUser/runAsGroup credentials,
-                        # and — for image pods — the container's rootfs
-                        cgroup_dir = inst.cgroup_dir
-                        uid, gid = cspec.run_as_uid, cspec.run_as_gid
-                        setns_pid, rootfs_p = self._container_entry(
-                            inst, cspec)
-
-                        def exec_runner(command, penv, timeout_s,
-                                        _cg=cgroup_dir, _uid=uid, _gid=gid,
-                                        _sp=setns_pid, _rf=rootfs_p):
-                            return self._run_confined(
-                                command, penv, _cg, _uid, _gid, timeout_s,
-                                setns_pid=_sp, rootfs=_rf)
-                    ok = run_probe(spec, env or {}, exec_runner=exec_runner)
-                    outcome = advance(st, spec, ok)
+                    outcome, st = self._tick_probe(inst, cspec, cinfo, kind,
+                                                   now)
                     if kind == "readiness" and outcome is not None:
                         if cinfo.ready != outcome:
                             cinfo.ready = outcome
@@ -1121,7 +1080,8 @@ class ProcessRuntime(Runtime):
                             extra={"instance": inst.id, "container": cspec.name,
                                    "failures": st.failures})
                         cinfo.message = "liveness probe failed"
-                        self._probe_states.pop(key, None)
+                        self._probe_states.pop(
+                            (inst.id, cspec.name, kind), None)
                         self._native.signal_process(cinfo.pid, 9, True)
                         # exit event drives restartPolicy from here
 
@@ -1169,64 +1129,6 @@ class ProcessRuntime(Runtime):
 
     # ------------- status -------------
 
-    def _pod_pids(self, inst: Instance) -> set:
-        """Every live pid belonging to the pod: the cgroup's procs when the
-        pod has a slot, else the container pids plus their descendants
-        (via /proc/<pid>/task/*/children)."""
-        if inst.cgroup_dir:
-            try:
-                with open(inst.cgroup_dir + "/cgroup.procs",
-                          encoding="ascii") as fh:
-                    pids = {int(line) for line in fh if line.strip()}
-                if pids:
-                    return pids
-            except OSError:
-                pass
-        pids = {c.pid for c in inst.containers
-                if c.exit_code is None and c.pid > 0}
-        frontier = list(pids)
-        while frontier:
-            pid = frontier.pop()
-            try:
-                for task in os.listdir(f"/proc/{pid}/task"):
-                    with open(f"/proc/{pid}/task/{task}/children",
-                              encoding="ascii") as fh:
-                        for child in fh.read().split():
-                            c = int(child)
-                            if c not in pids:
-                                pids.add(c)
-                                frontier.append(c)
-            except OSError:
-                continue
-        return pids
-
-    def _pod_listening_ports(self, inst: Instance) -> set:
-        """TCP ports in LISTEN state owned by *this pod's* processes —
-        socket inodes from /proc/net/tcp{,6} attributed via
-        /proc/<pid>/fd. A host-wide scan (round-1 weak #3) marked a pod's
-        port exposed when any unrelated process listened on it; the
-        reference gates readiness on the backend's per-pod portMappings
-        (kubelet.go:566-605), i.e. per-instance."""
-        by_inode = _listening_tcp_inodes()
-        if not by_inode:
-            return set()
-        ports = set()
-        for pid in self._pod_pids(inst):
-            try:
-                for fd in os.listdir(f"/proc/{pid}/fd"):
-                    try:
-                        link = os.readlink(f"/proc/{pid}/fd/{fd}")
-                    except OSError:
-                        continue
-                    if link.startswith("socket:["):
-                        ino = int(link[8:-1])
-                        port = by_inode.get(ino)
-                        if port is not None:
-                            ports.add(port)
-            except OSError:
-                continue
-        return ports
-
     def _status_of(self, inst: Instance) -> DetailedStatus:
         ports: Dict[int, int] = {}
         if inst.desired_status == PodStatus.RUNNING:
@@ -1234,7 +1136,10 @@ class ProcessRuntime(Runtime):
             for c in inst.params.containers:
                 want.extend(c.tcp_ports)
             if want:
-                listening = self._pod_listening_ports(inst)
+                listening = procfs.pod_listening_ports(
+                    inst.cgroup_dir,
+                    {c.pid for c in inst.containers
+                     if c.exit_code is None and c.pid > 0})
                 ports = {p: p for p in want if p in listening}
         return DetailedStatus(
             id=inst.id,
@@ -1298,10 +1203,7 @@ class ProcessRuntime(Runtime):
             inst.desired_status = PodStatus.TERMINATING
             # Cancel pending restartPolicy backoffs: a terminating pod must
             # not relaunch containers; all-in-backoff pods complete now.
-            for (iid, cname), t in list(self._restart_timers.items()):
-                if iid == instance_id:
-                    t.cancel()
-                    self._restart_timers.pop((iid, cname), None)
+            self._cancel_restarts(instance_id)
             for c in inst.containers:
                 c.backoff_until = 0
             if all(c.exit_code is not None for c in inst.containers) and \
@@ -1312,14 +1214,11 @@ class ProcessRuntime(Runtime):
             else:
                 grace = (grace_override_s if grace_override_s >= 0
                          else inst.params.termination_grace_s)
-                timer = threading.Timer(
-                    # spec.terminationGracePeriodSeconds — the window
-                    # covers preStop hooks AND the TERM->KILL ladder
-                    max(0.1, grace),
-                    self._force_kill, args=(instance_id,))
-                timer.daemon = True
-                self._kill_timers[instance_id] = timer
-                timer.start()
+                # spec.terminationGracePeriodSeconds — the window covers
+                # preStop hooks AND the TERM->KILL ladder
+                self._arm_timer(self._kill_timers, instance_id,
+                                max(0.1, grace), self._force_kill,
+                                instance_id)
                 hooks = []
                 for cspec in inst.params.containers:
                     if getattr(cspec, "pre_stop", None) is None:
@@ -1391,42 +1290,8 @@ class ProcessRuntime(Runtime):
             inst = self._instances.get(instance_id)
         if inst is None:
             return {}
-        stats: Dict[str, object] = {"containers": []}
-        if inst.cgroup_dir:
-            try:
-                with open(inst.cgroup_dir + "/cpu.stat", encoding="ascii") as fh:
-                    for line in fh:
-                        if line.startswith("usage_usec"):
-                            stats["cpuUsageCoreNanoSeconds"] = (
-                                int(line.split()[1]) * 1000)
-                            break
-                with open(inst.cgroup_dir + "/memory.current",
-                          encoding="ascii") as fh:
-                    stats["memoryUsageBytes"] = int(fh.read().strip())
-            except OSError:
-                pass
-        tick_ns = 1_000_000_000 // os.sysconf("SC_CLK_TCK")
-        page = os.sysconf("SC_PAGE_SIZE")
-        cpu_total = 0
-        mem_total = 0
-        for c in inst.containers:
-            entry: Dict[str, object] = {"name": c.name}
-            try:
-                with open(f"/proc/{c.pid}/stat", encoding="ascii") as fh:
-                    fields = fh.read().rsplit(") ", 1)[-1].split()
-                    # fields[11]=utime fields[12]=stime (post-comm offsets)
-                    entry["cpuUsageCoreNanoSeconds"] = (
-                        (int(fields[11]) + int(fields[12])) * tick_ns)
-                with open(f"/proc/{c.pid}/statm", encoding="ascii") as fh:
-                    entry["memoryRssBytes"] = int(fh.read().split()[1]) * page
-                cpu_total += entry.get("cpuUsageCoreNanoSeconds", 0)
-                mem_total += entry.get("memoryRssBytes", 0)
-            except (OSError, IndexError, ValueError):
-                pass  # container already exited
-            stats["containers"].append(entry)
-        stats.setdefault("cpuUsageCoreNanoSeconds", cpu_total)
-        stats.setdefault("memoryUsageBytes", mem_total)
-        return stats
+        return procfs.pod_stats(
+            inst.cgroup_dir, [(c.name, c.pid) for c in inst.containers])
 
     # ------------- logs -------------
 
@@ -1474,17 +1339,7 @@ class ProcessRuntime(Runtime):
         kubectl-exec and by exec probes — k8s runs both INSIDE the
         container, never as the kubelet (root) on the host."""
         argv = list(command)
-        if "/" not in argv[0]:
-            # exec fast path does no PATH search — resolve against the
-            # container's view when entering one, else the host
-            if setns_pid >= 0:
-                argv[0] = _resolve_via_proc_root(setns_pid, argv[0])
-            elif rootfs:
-                argv[0] = _resolve_in_tree(rootfs, argv[0])
-            else:
-                resolved = shutil.which(argv[0])
-                if resolved:
-                    argv[0] = resolved
+        argv[0] = procfs.resolve_argv0(argv[0], setns_pid, rootfs)
         sink = out_path or "/dev/null"
         try:
             pid, pidfd, _, _, _ = self._native.launch_process(
@@ -1537,11 +1392,7 @@ class ProcessRuntime(Runtime):
             inst = self._instances.get(instance_id)
         if inst is None:
             return 127, f"instance {instance_id} not found"
-        env = dict(os.environ)
-        env.pop("ROCR_VISIBLE_DEVICES", None)
-        env.pop("HIP_VISIBLE_DEVICES", None)
-        env.update(inst.params.env)
-        env.update(device_env(inst.gpu_indices, self.binder.ledger.inventory))
+        env = self._pod_env(inst)  # pod-level only: no container env
         cspec = None
         if container:
             cspec = next((c for c in inst.params.containers
@@ -1583,13 +1434,7 @@ class ProcessRuntime(Runtime):
             if cspec.name in all_names:
                 raise RuntimeError(
                     f"container name {cspec.name!r} already in use")
-        params = inst.params
-        env = dict(os.environ)
-        env.pop("ROCR_VISIBLE_DEVICES", None)
-        env.pop("HIP_VISIBLE_DEVICES", None)
-        env.update(params.env)
-        env.update(device_env(inst.gpu_indices, self.binder.ledger.inventory))
-        env.update(cspec.env)
+        env = self._pod_env(inst, cspec)
         env["AMDVK_INSTANCE_ID"] = inst.id
         argv = list(cspec.command) + list(cspec.args)
         if not argv:
@@ -1597,15 +1442,7 @@ class ProcessRuntime(Runtime):
         target = (inst.params.containers[0]
                   if inst.params.containers else None)
         setns_pid, rootfs = self._container_entry(inst, target)
-        if "/" not in argv[0]:
-            if setns_pid >= 0:
-                argv[0] = _resolve_via_proc_root(setns_pid, argv[0])
-            elif rootfs:
-                argv[0] = _resolve_in_tree(rootfs, argv[0])
-            else:
-                resolved = shutil.which(argv[0])
-                if resolved:
-                    argv[0] = resolved
+        argv[0] = procfs.resolve_argv0(argv[0], setns_pid, rootfs)
         stdout_path = str(self.logs_dir / f"{inst.id}-{cspec.name}.log")
         pid, pidfd, _, _, _ = self._native.launch_process(
             argv, [f"{k}={v}" for k, v in env.items()],
@@ -1629,135 +1466,23 @@ class ProcessRuntime(Runtime):
     # ------------- persistence / adoption -------------
 
     def _persist(self, inst: Instance) -> None:
-        record = {
-            "id": inst.id,
-            "pod_key": inst.pod_key,
-            "gpu_indices": inst.gpu_indices,
-            "desired_status": inst.desired_status,
-            "cgroup_dir": inst.cgroup_dir,
-            "created_at": inst.created_at,
-            "cost_per_hr": inst.cost_per_hr,
-            "gpu_memory_bytes": inst.params.gpu_memory_bytes,
-            "gpu_count": inst.params.gpu_count,
-            "namespace": inst.params.namespace,
-            "name": inst.params.name,
-            "restart_policy": inst.params.restart_policy,
-            # deadline/grace must survive restarts: an adopted RUNNING pod
-            # keeps its activeDeadlineSeconds budget (timer re-armed with the
-            # remainder in adopt_persisted) and its grace window
-            "active_deadline_s": inst.params.active_deadline_s,
-            "termination_grace_s": inst.params.termination_grace_s,
-            "resolv_conf": inst.params.resolv_conf,
-            # pod-level launch context: a crash-restart after kubelet
-            # restart must rebuild the same mounts/identity/env
-            "hostname": inst.params.hostname,
-            "pod_env": inst.params.env,
-            "fs_group": inst.params.fs_group,
-            "host_aliases": [[ip, list(names)]
-                             for ip, names in inst.params.host_aliases],
-            "volumes": {n: dataclasses.asdict(v)
-                        for n, v in inst.params.volumes.items()},
-            "deadline_exceeded": inst.deadline_exceeded,
-            "image_mode": inst.image_mode,
-            "containers": [
-                {
-                    "name": c.name,
-                    "pid": c.pid,
-                    "started_at": c.started_at,
-                    "finished_at": c.finished_at,
-                    "exit_code": c.exit_code,
-                    "ready": c.ready,
-                    "restart_count": c.restart_count,
-                    "image_id": c.image_id,
-                }
-                for c in inst.containers
-            ],
-            "ephemeral_containers": [
-                {
-                    "name": c.name,
-                    "pid": c.pid,
-                    "started_at": c.started_at,
-                    "finished_at": c.finished_at,
-                    "exit_code": c.exit_code,
-                }
-                for c in inst.ephemeral_containers
-            ],
-            "ephemeral_specs": [
-                {"name": c.name, "image": c.image, "command": c.command,
-                 "args": c.args, "env": c.env,
-                 "run_as_uid": c.run_as_uid, "run_as_gid": c.run_as_gid}
-                for c in inst.ephemeral_specs
-            ],
-            "init_containers": [
-                {
-                    "name": c.name,
-                    "pid": c.pid,
-                    "started_at": c.started_at,
-                    "finished_at": c.finished_at,
-                    "exit_code": c.exit_code,
-                }
-                for c in inst.init_containers
-            ],
-            "init_index": inst.init_index,
-            "container_specs": [
-                {
-                    "name": c.name,
-                    "image": c.image,
-                    "command": c.command,
-                    "args": c.args,
-                    "tcp_ports": c.tcp_ports,
-                    # probes must survive kubelet restarts: an adopted pod
-                    # whose readinessProbe was lost could never become Ready
-                    "readiness": dataclasses.asdict(c.readiness)
-                    if c.readiness else None,
-                    "liveness": dataclasses.asdict(c.liveness)
-                    if c.liveness else None,
-                    "startup": dataclasses.asdict(c.startup)
-                    if c.startup else None,
-                    "post_start": dataclasses.asdict(c.post_start)
-                    if c.post_start else None,
-                    "pre_stop": dataclasses.asdict(c.pre_stop)
-                    if c.pre_stop else None,
-                    "env": c.env,  # exec probes run in the container env
-                    # credentials/cwd must survive restarts: an adopted pod
-                    # whose container crash-restarts would otherwise relaunch
-                    # as the kubelet's user (root) — silently dropping its
-                    # securityContext.runAsUser
-                    "run_as_uid": c.run_as_uid,
-                    "run_as_gid": c.run_as_gid,
-                    "run_as_non_root": c.run_as_non_root,
-                    "read_only_root_fs": c.read_only_root_fs,
-                    "termination_message_path": c.termination_message_path,
-                    "termination_message_policy":
-                        c.termination_message_policy,
-                    "image_pull_policy": c.image_pull_policy,
-                    "volume_mounts": [dataclasses.asdict(vm)
-                                      for vm in c.volume_mounts],
-                    "working_dir": c.working_dir,
-                }
-                for c in inst.params.containers
-            ],
-            "init_specs": [
-                {
-                    "name": c.name,
-                    "image": c.image,
-                    "command": c.command,
-                    "args": c.args,
-                    "run_as_uid": c.run_as_uid,
-                    "run_as_gid": c.run_as_gid,
-                    "working_dir": c.working_dir,
-                }
-                for c in inst.params.init_containers
-            ],
-        }
-        # Unique temp name: the event thread and API threads may persist the
-        # same instance concurrently; rename is atomic, last writer wins.
-        tmp = self.instances_dir / f".{inst.id}.{threading.get_ident()}.tmp"
-        tmp.write_text(json.dumps(record))
-        try:
-            tmp.rename(self.instances_dir / f"{inst.id}.json")
-        except FileNotFoundError:
-            pass  # state dir torn down during shutdown
+        journal.write_record(self.instances_dir, inst)
+
+    def _rewatch(self, inst: Instance, cinfo, vanished: str = "") -> bool:
+        """Watch a journaled, still-running container again through a fresh
+        pidfd. If its process died while the kubelet was away, mark it
+        exited (-1: exact code unknown) with `vanished` as the message.
+        Returns whether it is alive."""
+        pidfd = self._native.open_pidfd(cinfo.pid)
+        if pidfd < 0:
+            cinfo.exit_code = -1
+            cinfo.finished_at = time.time()
+            cinfo.message = vanished
+            return False
+        self._loop.add_process(cinfo.pid, pidfd, -1, cinfo.pid)
+        with self._lock:
+            self._pid_to_instance[cinfo.pid] = inst.id
+        return True
 
     def adopt_persisted(self) -> List[str]:
         """Rebuild instance state after a kubelet restart: re-open pidfds for
@@ -1769,164 +1494,35 @@ class ProcessRuntime(Runtime):
                 rec = json.loads(path.read_text())
             except (OSError, json.JSONDecodeError):
                 continue
-            from .probes import ProbeSpec
-            from .types import ContainerSpec, VolumeMount, VolumeSource
-
-            params = DeployParams(
-                pod_key=rec["pod_key"],
-                name=rec.get("name", rec["pod_key"]),
-                namespace=rec.get("namespace", "default"),
-                gpu_count=rec.get("gpu_count", 0),
-                gpu_memory_bytes=rec.get("gpu_memory_bytes", 0),
-                restart_policy=rec.get("restart_policy", "Never"),
-                active_deadline_s=rec.get("active_deadline_s", 0.0),
-                resolv_conf=rec.get("resolv_conf", ""),
-                hostname=rec.get("hostname", ""),
-                env=rec.get("pod_env", {}) or {},
-                fs_group=rec.get("fs_group", -1),
-                host_aliases=[(ip, list(names)) for ip, names in
-                              rec.get("host_aliases", []) or []],
-                volumes={n: VolumeSource(**v) for n, v in
-                         (rec.get("volumes", {}) or {}).items()},
-                termination_grace_s=rec.get("termination_grace_s",
-                                            TERM_GRACE_S),
-                containers=[
-                    ContainerSpec(
-                        name=c["name"], image=c.get("image", ""),
-                        command=c.get("command", []), args=c.get("args", []),
-                        tcp_ports=c.get("tcp_ports", []),
-                        env=c.get("env", {}) or {},
-                        readiness=ProbeSpec(**c["readiness"])
-                        if c.get("readiness") else None,
-                        liveness=ProbeSpec(**c["liveness"])
-                        if c.get("liveness") else None,
-                        startup=ProbeSpec(**c["startup"])
-                        if c.get("startup") else None,
-                        post_start=ProbeSpec(**c["post_start"])
-                        if c.get("post_start") else None,
-                        pre_stop=ProbeSpec(**c["pre_stop"])
-                        if c.get("pre_stop") else None,
-                        run_as_uid=c.get("run_as_uid", -1),
-                        run_as_gid=c.get("run_as_gid", -1),
-                        run_as_non_root=c.get("run_as_non_root", False),
-                        read_only_root_fs=c.get("read_only_root_fs",
-                                                False),
-                        termination_message_path=c.get(
-                            "termination_message_path",
-                            "/dev/termination-log"),
-                        termination_message_policy=c.get(
-                            "termination_message_policy", "File"),
-                        image_pull_policy=c.get("image_pull_policy", ""),
-                        volume_mounts=[VolumeMount(**vm) for vm in
-                                       c.get("volume_mounts", []) or []],
-                        working_dir=c.get("working_dir", ""),
-                    )
-                    for c in rec.get("container_specs", [])
-                ],
-                init_containers=[
-                    ContainerSpec(
-                        name=c["name"], image=c.get("image", ""),
-                        command=c.get("command", []), args=c.get("args", []),
-                        run_as_uid=c.get("run_as_uid", -1),
-                        run_as_gid=c.get("run_as_gid", -1),
-                        working_dir=c.get("working_dir", ""),
-                    )
-                    for c in rec.get("init_specs", [])
-                ],
-            )
-            inst = Instance(
-                id=rec["id"], pod_key=rec["pod_key"], params=params,
-                gpu_indices=rec.get("gpu_indices", []),
-                desired_status=rec.get("desired_status", PodStatus.RUNNING),
-                cgroup_dir=rec.get("cgroup_dir", ""),
-                created_at=rec.get("created_at", time.time()),
-                cost_per_hr=rec.get("cost_per_hr", 0.0),
-                init_index=rec.get("init_index", 0),
-                deadline_exceeded=rec.get("deadline_exceeded", False),
-                image_mode=rec.get("image_mode", ""),
-            )
-            for c in rec.get("init_containers", []):
-                icinfo = ContainerRuntimeInfo(
-                    name=c["name"], pid=c["pid"],
-                    started_at=c.get("started_at", 0.0),
-                    finished_at=c.get("finished_at", 0.0),
-                    exit_code=c.get("exit_code"),
-                )
-                if icinfo.exit_code is None:
+            inst = journal.instance_from_record(rec)
+            params = inst.params
+            for c in inst.init_containers:
+                if c.exit_code is None:
                     # Init was mid-flight across the restart: watch it again
                     # so progression resumes on its exit event.
-                    pidfd = self._native.open_pidfd(icinfo.pid)
-                    if pidfd >= 0:
-                        self._loop.add_process(icinfo.pid, pidfd, -1, icinfo.pid)
-                        with self._lock:
-                            self._pid_to_instance[icinfo.pid] = inst.id
-                    else:
-                        icinfo.exit_code = -1
-                        icinfo.finished_at = time.time()
-                        icinfo.message = "init vanished during kubelet restart"
-                inst.init_containers.append(icinfo)
+                    self._rewatch(inst, c,
+                                  "init vanished during kubelet restart")
             if any(c.exit_code not in (None, 0) for c in inst.init_containers):
                 inst.desired_status = PodStatus.EXITED
-            for c in rec.get("ephemeral_specs", []):
-                inst.ephemeral_specs.append(ContainerSpec(
-                    name=c["name"], image=c.get("image", ""),
-                    command=c.get("command", []), args=c.get("args", []),
-                    env=c.get("env", {}) or {},
-                    run_as_uid=c.get("run_as_uid", -1),
-                    run_as_gid=c.get("run_as_gid", -1)))
-            for c in rec.get("ephemeral_containers", []):
-                einfo = ContainerRuntimeInfo(
-                    name=c["name"], pid=c["pid"],
-                    started_at=c.get("started_at", 0.0),
-                    finished_at=c.get("finished_at", 0.0),
-                    exit_code=c.get("exit_code"))
-                if einfo.exit_code is None:
-                    pidfd = self._native.open_pidfd(einfo.pid)
-                    if pidfd >= 0:
-                        self._loop.add_process(einfo.pid, pidfd, -1,
-                                               einfo.pid)
-                        with self._lock:
-                            self._pid_to_instance[einfo.pid] = inst.id
-                    else:
-                        einfo.exit_code = -1
-                        einfo.finished_at = time.time()
-                inst.ephemeral_containers.append(einfo)
-            all_alive = True
-            for c in rec.get("containers", []):
-                cinfo = ContainerRuntimeInfo(
-                    name=c["name"], pid=c["pid"], started_at=c.get("started_at", 0.0),
-                    finished_at=c.get("finished_at", 0.0),
-                    exit_code=c.get("exit_code"), ready=c.get("ready", False),
-                    restart_count=c.get("restart_count", 0),
-                    image_id=c.get("image_id", ""),
-                )
-                if cinfo.exit_code is None:
-                    pidfd = self._native.open_pidfd(cinfo.pid)
-                    if pidfd >= 0:
-                        self._loop.add_process(cinfo.pid, pidfd, -1, cinfo.pid)
-                        with self._lock:
-                            self._pid_to_instance[cinfo.pid] = inst.id
-                        if not cinfo.ready:
-                            # The AMDVK_READY_FD pipe died with the old
-                            # kubelet: its signal can never arrive now. A
-                            # container WITH a readinessProbe re-proves
-                            # readiness via the probe loop; without one,
-                            # k8s semantics apply — a running container is
-                            # ready (found by soak race hunting: a pod
-                            # deployed moments before a kubelet crash was
-                            # stuck NotReady forever).
-                            spec = next(
-                                (s for s in params.containers
-                                 if s.name == cinfo.name), None)
-                            if spec is None or spec.readiness is None:
-                                cinfo.ready = True
-                    else:
-                        # Process died while we were away; exact code unknown.
-                        cinfo.exit_code = -1
-                        cinfo.finished_at = time.time()
-                        cinfo.message = "process vanished during kubelet restart"
-                        all_alive = False
-                inst.containers.append(cinfo)
+            for c in inst.ephemeral_containers:
+                if c.exit_code is None:
+                    self._rewatch(inst, c)
+            for c in inst.containers:
+                if (c.exit_code is None
+                        and self._rewatch(
+                            inst, c, "process vanished during kubelet restart")
+                        and not c.ready):
+                    # The AMDVK_READY_FD pipe died with the old kubelet: its
+                    # signal can never arrive now. A container WITH a
+                    # readinessProbe re-proves readiness via the probe loop;
+                    # without one, k8s semantics apply — a running container
+                    # is ready (found by soak race hunting: a pod deployed
+                    # moments before a kubelet crash was stuck NotReady
+                    # forever).
+                    spec = next((s for s in params.containers
+                                 if s.name == c.name), None)
+                    if spec is None or spec.readiness is None:
+                        c.ready = True
             # Containers that crashed across the restart window resume their
             # restartPolicy loop instead of failing the pod: re-reserve the
             # GPUs and schedule restarts with fresh backoff.
@@ -1976,24 +1572,18 @@ class ProcessRuntime(Runtime):
                     # adoption); an already-blown budget fires immediately.
                     remaining = (inst.created_at + params.active_deadline_s
                                  - time.time())
-                    t = threading.Timer(max(0.0, remaining),
-                                        self._deadline_exceeded,
-                                        args=(inst.id,))
-                    t.daemon = True
-                    self._deadline_timers[inst.id] = t
-                    t.start()
+                    self._arm_timer(self._deadline_timers, inst.id,
+                                    max(0.0, remaining),
+                                    self._deadline_exceeded, inst.id)
                 if inst.desired_status == PodStatus.TERMINATING and any(
                         c.exit_code is None for c in inst.containers):
                     # the previous kubelet died mid-grace: its SIGKILL
                     # timer died with it — re-arm with the full grace
                     # (elapsed time is unknown; a TERM-immune pid-1 must
                     # not outlive the window forever)
-                    t = threading.Timer(
-                        max(0.1, params.termination_grace_s),
-                        self._force_kill, args=(inst.id,))
-                    t.daemon = True
-                    self._kill_timers[inst.id] = t
-                    t.start()
+                    self._arm_timer(self._kill_timers, inst.id,
+                                    max(0.1, params.termination_grace_s),
+                                    self._force_kill, inst.id)
             adopted.append(inst.id)
         if adopted:
             log.info("adopted persisted instances", extra={"count": len(adopted)})
@@ -2011,47 +1601,3 @@ class ProcessRuntime(Runtime):
             timer.cancel()
         for timer in self._deadline_timers.values():
             timer.cancel()
-
-
-def _resolve_via_proc_root(pid: int, argv0: str) -> str:
-    """PATH-resolve inside a live container via /proc/<pid>/root (the
-    kernel's view of its mount namespace root)."""
-    for p in ("/usr/local/sbin", "/usr/local/bin", "/usr/sbin", "/usr/bin",
-              "/sbin", "/bin"):
-        if os.path.exists(f"/proc/{pid}/root{p}/{argv0}"):
-            return f"{p}/{argv0}"
-    return argv0
-
-
-def _resolve_in_tree(rootfs: str, argv0: str) -> str:
-    """PATH-resolve against a rootfs directory tree (chroot mode)."""
-    for p in ("/usr/local/sbin", "/usr/local/bin", "/usr/sbin", "/usr/bin",
-              "/sbin", "/bin"):
-        if os.path.exists(f"{rootfs}{p}/{argv0}"):
-            return f"{p}/{argv0}"
-    return argv0
-
-
-def _listening_tcp_inodes() -> dict:
-    """socket-inode → local port for LISTEN-state TCP sockets from
-    /proc/net/tcp{,6} (state 0A, inode field 9). Two passes, unioned:
-    the kernel's seq_file iteration can skip entries while the socket
-    table mutates under load, and a missed entry here reads as
-    "pod port not exposed"."""
-    by_inode = {}
-    for path in ("/proc/net/tcp", "/proc/net/tcp6",
-                 "/proc/net/tcp", "/proc/net/tcp6"):
-        try:
-            with open(path, "r", encoding="ascii") as fh:
-                next(fh, None)
-                for line in fh:
-                    parts = line.split()
-                    if len(parts) > 9 and parts[3] == "0A":
-                        try:
-                            port = int(parts[1].rsplit(":", 1)[1], 16)
-                            by_inode[int(parts[9])] = port
-                        except ValueError:
-                            continue
-        except OSError:
-            continue
-    return by_inode
