@@ -31,7 +31,8 @@ from .binder import device_env
 log = logging.getLogger("gpu.diagnostics")
 
 # gpucheck exit codes (ops/gpucheck/gpucheck.hip)
-EXIT_STAGES = {2: "usage", 11: "hip", 20: "hbm", 21: "mfma", 22: "bandwidth"}
+EXIT_STAGES = {2: "usage", 11: "hip", 20: "hbm", 21: "mfma", 22: "bandwidth",
+               23: "copy"}
 RESERVATION_PREFIX = "amdvk-system/gpucheck-"
 
 
@@ -48,8 +49,8 @@ class GpuCheckResult:
     gpu: int
     ok: bool
     exit_code: Optional[int] = None
-    # "" on a pass; otherwise the failing stage ("hbm", "mfma", "bandwidth",
-    # "hip", "usage") or "timeout", "signal N", "bad-output".
+    # "" on a pass; otherwise the failing stage ("hbm", "copy", "mfma",
+    # "bandwidth", "hip", "usage") or "timeout", "signal N", "bad-output".
     reason: str = ""
     data: Dict[str, Any] = field(default_factory=dict)  # the binary's JSON
     duration_s: float = 0.0
@@ -347,8 +348,8 @@ def main(argv=None) -> int:
         prog="python -m k8s_runpod_kubelet_amd.gpu.diagnostics",
         description="Run the active GPU self-test on one GPU and print its "
                     "JSON. Exits with the gpucheck exit code (0 pass, 20 HBM, "
-                    "21 MFMA, 22 bandwidth, 11 HIP error; 1 for a timeout, "
-                    "signal or unparsable output).")
+                    "23 copy mismatch, 21 MFMA, 22 bandwidth, 11 HIP "
+                    "error; 1 for a timeout, signal or unparsable output).")
     p.add_argument("--gpu", type=int, required=True)
     p.add_argument("--bytes", default="1G")
     p.add_argument("--timeout", type=float, default=60.0)

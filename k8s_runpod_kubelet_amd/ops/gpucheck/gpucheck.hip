@@ -3,15 +3,22 @@
 // Tests visible device 0 (the caller scopes visibility with
 // ROCR_VISIBLE_DEVICES) in three stages:
 //   1. HBM fill + verify with a hashed 16-byte pattern and its complement,
-//   2. device-to-device copy bandwidth,
+//   2. device-to-device copy bandwidth, with the copied half verified against
+//      the pattern its source holds,
 //   3. an exact-integer MFMA self-test (bf16 32x32x16, no memory loads).
 // Prints exactly one JSON object as the last stdout line and exits with a
-// stage-specific code:
-//   0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, 21 MFMA mismatch,
-//   22 copy bandwidth below --min-copy-gbs.
+// stage-specific code (the first that applies, in this order):
+//   0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, 23 copy mismatch,
+//   21 MFMA mismatch, 22 copy bandwidth below --min-copy-gbs.
 // `--cpu` runs the HBM stage as host loops over malloc'ed memory and makes no
 // HIP call, so the CLI, JSON and mismatch localisation are testable without
-// a GPU.
+// a GPU. With an explicit --mfma-waves it also fills the MFMA tiles with a
+// host integer matmul and runs the same comparison over them.
+//
+// Flags that exist for the test suite: --dump-pattern, --dump-vectors,
+// --store-variant, --inject-flip, --inject-pass, --inject-copy-flip,
+// --dump-mfma-tile, --inject-mfma. The injections flip bits in the region
+// or in the host copy of the MFMA result; they test the checkers.
 //
 // Build: hipcc --offload-arch=gfx950 -O2 -std=c++17 gpucheck.hip -o gpucheck
 
@@ -176,11 +183,29 @@ struct Options {
   uint64_t seed = 0x6770756368656B31ull;
   double min_copy_gbs = 0.0;
   long mfma_waves = -1;  // -1: 8 x multiProcessorCount
-  bool inject = false;
-  size_t inject_offset = 0;
-  int inject_bit = 0;
+  struct Flip {
+    size_t offset;
+    int bit;
+  };
+  std::vector<Flip> flips;  // applied after the fill of pass inject_pass
+  uint32_t inject_pass = 0;
+  bool copy_flip = false;  // applied to the destination half after the copy
+  Flip copy_flip_at{0, 0};
   bool dump_pattern = false;
+  std::vector<size_t> dump_vectors;
+  int store_variant = -1;  // -1 auto, 0 plain, 1 non-temporal
+  long dump_mfma_tile = -1;
+  struct MfmaInject {
+    long wave;
+    int elem;
+  };
+  std::vector<MfmaInject> mfma_inject;
 };
+
+constexpr size_t kMaxFlips = 16;
+constexpr size_t kMaxDumpVectors = 16;
+constexpr size_t kMaxMfmaInject = 8;
+const char* const kVariantNames[2] = {"plain", "nontemporal"};
 
 bool parse_u64(const char* s, uint64_t* out, bool allow_suffix) {
   if (s == nullptr || *s == '\0' || *s == '-' || *s == '+') return false;
@@ -223,9 +248,26 @@ int usage(const char* why, const char* arg) {
           "usage: gpucheck [--cpu] [--bytes N[K|M|G]] [--passes P] "
           "[--base-index N] [--seed S]\n"
           "                [--min-copy-gbs X] [--mfma-waves W] "
-          "[--inject-flip OFFSET:BIT]\n",
+          "[--store-variant plain|nontemporal|auto]\n"
+          "       checks of the checkers:\n"
+          "                [--dump-pattern] [--dump-vectors I[,J,...]] "
+          "[--dump-mfma-tile W]\n"
+          "                [--inject-flip OFFSET:BIT]... [--inject-pass P] "
+          "[--inject-copy-flip OFFSET:BIT]\n"
+          "                [--inject-mfma WAVE:ELEM]...\n"
+          "exit: 0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, "
+          "23 copy mismatch, 21 MFMA mismatch,\n"
+          "      22 copy bandwidth below --min-copy-gbs\n",
           why, arg ? " " : "", arg ? arg : "");
   return 2;
+}
+
+// "A:B", both unsigned integers.
+bool parse_pair(const char* v, uint64_t* a, uint64_t* b) {
+  const char* colon = v ? strchr(v, ':') : nullptr;
+  return colon != nullptr &&
+         parse_u64(std::string(v, colon - v).c_str(), a, false) &&
+         parse_u64(colon + 1, b, false);
 }
 
 // Returns 0 on success, 2 on a usage error.
@@ -262,24 +304,86 @@ int parse_args(int argc, char** argv, Options* o) {
         return usage("bad value for", "--mfma-waves");
       o->mfma_waves = static_cast<long>(u);
     } else if (a == "--inject-flip") {
-      const char* v = next();
-      const char* colon = v ? strchr(v, ':') : nullptr;
       uint64_t bit = 0;
-      if (colon == nullptr ||
-          !parse_u64(std::string(v, colon - v).c_str(), &u, false) ||
-          !parse_u64(colon + 1, &bit, false) || bit > 7)
+      if (!parse_pair(next(), &u, &bit) || bit > 7)
         return usage("bad value for", "--inject-flip");
-      o->inject = true;
-      o->inject_offset = static_cast<size_t>(u);
-      o->inject_bit = static_cast<int>(bit);
+      if (o->flips.size() == kMaxFlips)
+        return usage("too many", "--inject-flip");
+      o->flips.push_back({static_cast<size_t>(u), static_cast<int>(bit)});
+    } else if (a == "--inject-pass") {
+      if (!parse_u64(next(), &u, false) || u >= 1024)
+        return usage("bad value for", "--inject-pass");
+      o->inject_pass = static_cast<uint32_t>(u);
+    } else if (a == "--inject-copy-flip") {
+      uint64_t bit = 0;
+      if (!parse_pair(next(), &u, &bit) || bit > 7)
+        return usage("bad value for", "--inject-copy-flip");
+      o->copy_flip = true;
+      o->copy_flip_at = {static_cast<size_t>(u), static_cast<int>(bit)};
+    } else if (a == "--dump-vectors") {
+      const char* v = next();
+      if (v == nullptr) return usage("bad value for", "--dump-vectors");
+      std::string rest = v;
+      for (;;) {
+        const size_t comma = rest.find(',');
+        if (!parse_u64(rest.substr(0, comma).c_str(), &u, false))
+          return usage("bad value for", "--dump-vectors");
+        if (o->dump_vectors.size() == kMaxDumpVectors)
+          return usage("too many indices for", "--dump-vectors");
+        o->dump_vectors.push_back(static_cast<size_t>(u));
+        if (comma == std::string::npos) break;
+        rest = rest.substr(comma + 1);
+      }
+    } else if (a == "--store-variant") {
+      const char* v = next();
+      const std::string s = v ? v : "";
+      if (s == "auto") o->store_variant = -1;
+      else if (s == kVariantNames[0]) o->store_variant = 0;
+      else if (s == kVariantNames[1]) o->store_variant = 1;
+      else return usage("bad value for", "--store-variant");
+    } else if (a == "--dump-mfma-tile") {
+      if (!parse_u64(next(), &u, false) || u >= 65536)
+        return usage("bad value for", "--dump-mfma-tile");
+      o->dump_mfma_tile = static_cast<long>(u);
+    } else if (a == "--inject-mfma") {
+      uint64_t elem = 0;
+      if (!parse_pair(next(), &u, &elem) || u >= 65536 || elem >= 32 * 32)
+        return usage("bad value for", "--inject-mfma");
+      if (o->mfma_inject.size() == kMaxMfmaInject)
+        return usage("too many", "--inject-mfma");
+      o->mfma_inject.push_back({static_cast<long>(u), static_cast<int>(elem)});
     } else {
       return usage("unknown argument", a.c_str());
     }
   }
   if (o->bytes < 16) o->bytes = 16;
   o->bytes &= ~static_cast<size_t>(15);
-  if (o->inject && o->inject_offset >= o->bytes)
-    return usage("--inject-flip offset is outside the region", nullptr);
+  const size_t nvec = o->bytes / 16;
+  for (const Options::Flip& f : o->flips)
+    if (f.offset >= o->bytes)
+      return usage("--inject-flip offset is outside the region", nullptr);
+  if (o->inject_pass >= o->passes)
+    return usage("--inject-pass must be below --passes", nullptr);
+  for (size_t i : o->dump_vectors)
+    if (i >= nvec)
+      return usage("--dump-vectors index is outside the region", nullptr);
+  // The copy moves vectors [0, half) to [half, 2*half).
+  const size_t half = nvec / 2;
+  if (o->copy_flip && (o->copy_flip_at.offset < half * 16 ||
+                       o->copy_flip_at.offset >= 2 * half * 16))
+    return usage("--inject-copy-flip offset is outside the destination half",
+                 nullptr);
+  return 0;
+}
+
+// The MFMA flags name waves, and how many waves run is known only once the
+// device is. 0 waves: the stage does not run.
+int check_mfma_args(const Options& o, long nwaves) {
+  if (o.dump_mfma_tile >= nwaves)
+    return usage("--dump-mfma-tile wave is outside the run", nullptr);
+  for (const Options::MfmaInject& m : o.mfma_inject)
+    if (m.wave >= nwaves)
+      return usage("--inject-mfma wave is outside the run", nullptr);
   return 0;
 }
 
@@ -298,12 +402,25 @@ struct Report {
   double write_gbs_plain = 0, write_gbs_nontemporal = 0;
   const char* store_variant = "plain";
   std::vector<std::string> pattern_dump;
-  // bandwidth
+  struct VecDump {
+    size_t index;
+    uint32_t pass;
+    std::string value;
+  };
+  std::vector<VecDump> vector_dump;  // as read back from the region
+  // copy: bandwidth and the verification of what was copied
   const char* bandwidth = "skipped";
   double copy_gbs = 0;
+  const char* copy = "skipped";
+  uint64_t copy_mismatch_vectors = 0;
+  bool have_copy_first_bad = false;
+  uint64_t copy_first_bad_offset = 0;  // within the whole region
+  Vec16 copy_first_bad_xor{0, 0};
   // MFMA
   const char* mfma = "skipped";
   long mfma_waves = 0, mfma_bad_waves = 0, mfma_first_bad_wave = -1;
+  bool mfma_tile_valid = false;
+  std::vector<int> mfma_tile;
 };
 
 std::string hex128(const Vec16& v) {
@@ -428,11 +545,17 @@ struct GpuBackend : Backend {
     return timer.end();
   }
   double verify(uint32_t pass, uint64_t* bad, uint64_t* first) override {
+    return verify_range(0, nvec, pass, bad, first);
+  }
+  // Checks that vectors [at, at + n) hold the pattern of logical indices
+  // base_index + 0..n-1; *first is relative to `at`.
+  double verify_range(size_t at, size_t n, uint32_t pass, uint64_t* bad,
+                      uint64_t* first) {
     const unsigned long long init[2] = {0ull, kNoBad};
     HIP_CHECK(hipMemcpy(counters, init, sizeof(init), hipMemcpyHostToDevice));
     timer.begin();
-    hipLaunchKernelGGL(hbm_verify, dim3(grid_for(nvec)), dim3(kBlock), 0, 0,
-                       mem, nvec, o.base_index, o.seed, pass, counters);
+    hipLaunchKernelGGL(hbm_verify, dim3(grid_for(n)), dim3(kBlock), 0, 0,
+                       mem + at, n, o.base_index, o.seed, pass, counters);
     const double s = timer.end();
     unsigned long long got[2];
     HIP_CHECK(hipMemcpy(got, counters, sizeof(got), hipMemcpyDeviceToHost));
@@ -452,18 +575,31 @@ struct GpuBackend : Backend {
 
 // ------------------------------------------------------------------ stages
 
+void flip_bit(Backend& be, const Options::Flip& f) {
+  const size_t vi = f.offset / 16;
+  Vec16 v = be.read_vec(vi);
+  unsigned char raw[16];
+  memcpy(raw, &v, 16);
+  raw[f.offset % 16] ^= static_cast<unsigned char>(1u << f.bit);
+  memcpy(&v, raw, 16);
+  be.write_vec(vi, v);
+}
+
 void run_hbm(Backend& be, const Options& o, Report* rep) {
   const size_t nvec = o.bytes / 16;
   const double bytes = static_cast<double>(o.bytes);
-  int variant = 0;
+  const bool forced = o.store_variant >= 0;
+  int variant = forced ? o.store_variant : 0;
+  if (forced) rep->store_variant = kVariantNames[variant];
   if (o.dump_pattern) {
+    // What the host expects, not what the region holds: see --dump-vectors.
     for (size_t i = 0; i < std::min<size_t>(nvec, 4); ++i)
       rep->pattern_dump.push_back(
           hex128(gpucheck::pattern(o.seed, 0, o.base_index + i)));
   }
   for (uint32_t pass = 0; pass < o.passes; ++pass) {
     double write_s;
-    if (pass == 0 && be.store_variants() > 1) {
+    if (pass == 0 && !forced && be.store_variants() > 1) {
       // Both variants write the same data; keep the faster for later passes.
       const double plain_s = be.fill(0, 0);
       const double nt_s = be.fill(0, 1);
@@ -476,15 +612,8 @@ void run_hbm(Backend& be, const Options& o, Report* rep) {
       write_s = be.fill(pass, variant);
     }
     rep->write_gbs = std::max(rep->write_gbs, gbs(bytes, write_s));
-    if (pass == 0 && o.inject) {
-      const size_t vi = o.inject_offset / 16;
-      Vec16 v = be.read_vec(vi);
-      unsigned char raw[16];
-      memcpy(raw, &v, 16);
-      raw[o.inject_offset % 16] ^= static_cast<unsigned char>(1u << o.inject_bit);
-      memcpy(&v, raw, 16);
-      be.write_vec(vi, v);
-    }
+    if (pass == o.inject_pass)
+      for (const Options::Flip& f : o.flips) flip_bit(be, f);
     uint64_t bad = 0, first = kNoBad;
     const double read_s = be.verify(pass, &bad, &first);
     rep->read_gbs = std::max(rep->read_gbs, gbs(bytes, read_s));
@@ -498,7 +627,14 @@ void run_hbm(Backend& be, const Options& o, Report* rep) {
       rep->first_bad_xor = Vec16{got.lo ^ want.lo, got.hi ^ want.hi};
     }
   }
-  if (be.store_variants() == 1) rep->write_gbs_plain = rep->write_gbs;
+  // A run of one variant reports that variant's bandwidth and 0 for the other.
+  if (forced)
+    (variant ? rep->write_gbs_nontemporal : rep->write_gbs_plain) =
+        rep->write_gbs;
+  else if (be.store_variants() == 1)
+    rep->write_gbs_plain = rep->write_gbs;
+  for (size_t i : o.dump_vectors)
+    rep->vector_dump.push_back({i, o.passes - 1, hex128(be.read_vec(i))});
 }
 
 void run_copy(GpuBackend& be, const Options& o, Report* rep) {
@@ -516,10 +652,112 @@ void run_copy(GpuBackend& be, const Options& o, Report* rep) {
   rep->copy_gbs = gbs(2.0 * 16.0 * static_cast<double>(half), times[times.size() / 2]);
   rep->bandwidth =
       (o.min_copy_gbs > 0 && rep->copy_gbs < o.min_copy_gbs) ? "fail" : "pass";
+
+  // The source half still holds the last pass's pattern for indices
+  // 0..half-1, so the destination half must verify against exactly that.
+  // With an odd vector count the last vector belongs to neither half.
+  if (o.copy_flip) flip_bit(be, o.copy_flip_at);
+  const uint32_t pass = o.passes - 1;
+  uint64_t bad = 0, first = kNoBad;
+  be.verify_range(half, half, pass, &bad, &first);
+  rep->copy_mismatch_vectors = bad;
+  rep->copy = bad ? "fail" : "pass";
+  if (bad != 0 && first < half) {
+    const Vec16 got = be.read_vec(half + static_cast<size_t>(first));
+    const Vec16 want = gpucheck::pattern(o.seed, pass, o.base_index + first);
+    rep->have_copy_first_bad = true;
+    rep->copy_first_bad_offset = (half + first) * 16;
+    rep->copy_first_bad_xor = Vec16{got.lo ^ want.lo, got.hi ^ want.hi};
+  }
 }
 
-void run_mfma(const Options& o, int compute_units, Report* rep) {
-  const long nwaves = o.mfma_waves > 0 ? o.mfma_waves : 8L * compute_units;
+// The 32x32 tile wave `w` must produce, as integers, row-major.
+void mfma_expected_tile(uint64_t seed, long w, int* out) {
+  using gpucheck::kMfmaK;
+  std::vector<int> a(32 * kMfmaK), bt(32 * kMfmaK);
+  const uint64_t key_a = gpucheck::mfma_key(seed, static_cast<uint32_t>(w), 0);
+  const uint64_t key_b = gpucheck::mfma_key(seed, static_cast<uint32_t>(w), 1);
+  for (int r = 0; r < 32; ++r)
+    for (int k = 0; k < kMfmaK; ++k) {
+      a[r * kMfmaK + k] = gpucheck::mfma_a(key_a, r, k);
+      bt[r * kMfmaK + k] = gpucheck::mfma_b(key_b, k, r);  // B transposed
+    }
+  for (int row = 0; row < 32; ++row)
+    for (int col = 0; col < 32; ++col) {
+      int sum = 0;
+      for (int k = 0; k < kMfmaK; ++k)
+        sum += a[row * kMfmaK + k] * bt[col * kMfmaK + k];
+      out[row * 32 + col] = sum;
+    }
+}
+
+// bad[w] != 0 where tile w of `host` differs from the expected product.
+std::vector<char> mfma_compare(const std::vector<float>& host, long nwaves,
+                               uint64_t seed) {
+  std::vector<char> bad(static_cast<size_t>(nwaves), 0);
+  std::vector<int> want(32 * 32);
+  for (long w = 0; w < nwaves; ++w) {
+    mfma_expected_tile(seed, w, want.data());
+    const float* tile = host.data() + static_cast<size_t>(w) * 32 * 32;
+    // Every value is an integer of magnitude <= 1152, so equality of the
+    // floats is bit-exactness (NaN compares unequal and is caught).
+    for (int e = 0; e < 32 * 32; ++e)
+      if (!(tile[e] == static_cast<float>(want[e]))) {
+        bad[w] = 1;
+        break;
+      }
+  }
+  return bad;
+}
+
+// Everything after the tiles are in host memory: the dump, the injections,
+// the comparison and the verdict.
+void judge_mfma(std::vector<float>& host, long nwaves, const Options& o,
+                Report* rep) {
+  rep->mfma_waves = nwaves;
+  bool dump_bad = false;
+  if (o.dump_mfma_tile >= 0) {
+    const float* tile =
+        host.data() + static_cast<size_t>(o.dump_mfma_tile) * 32 * 32;
+    rep->mfma_tile_valid = true;
+    for (int e = 0; e < 32 * 32; ++e) {
+      const float v = tile[e];
+      // Not a finite integer an int can hold: no dump, and the wave is bad.
+      if (!(v >= -16777216.0f && v <= 16777216.0f) ||
+          v != static_cast<float>(static_cast<int>(v))) {
+        rep->mfma_tile_valid = false;
+        dump_bad = true;
+        break;
+      }
+      rep->mfma_tile.push_back(static_cast<int>(v));
+    }
+  }
+  for (const Options::MfmaInject& m : o.mfma_inject)
+    host[static_cast<size_t>(m.wave) * 32 * 32 + m.elem] += 1.0f;
+  std::vector<char> bad = mfma_compare(host, nwaves, o.seed);
+  if (dump_bad) bad[o.dump_mfma_tile] = 1;
+  for (long w = 0; w < nwaves; ++w)
+    if (bad[w]) {
+      if (rep->mfma_bad_waves == 0) rep->mfma_first_bad_wave = w;
+      ++rep->mfma_bad_waves;
+    }
+  rep->mfma = rep->mfma_bad_waves ? "fail" : "pass";
+}
+
+// --cpu: the tiles come from the host integer matmul, so this exercises
+// judge_mfma and the JSON, not a device.
+void run_mfma_cpu(const Options& o, long nwaves, Report* rep) {
+  std::vector<float> host(static_cast<size_t>(nwaves) * 32 * 32);
+  std::vector<int> tile(32 * 32);
+  for (long w = 0; w < nwaves; ++w) {
+    mfma_expected_tile(o.seed, w, tile.data());
+    for (int e = 0; e < 32 * 32; ++e)
+      host[static_cast<size_t>(w) * 32 * 32 + e] = static_cast<float>(tile[e]);
+  }
+  judge_mfma(host, nwaves, o, rep);
+}
+
+void run_mfma(const Options& o, long nwaves, Report* rep) {
   const size_t nfloat = static_cast<size_t>(nwaves) * 32 * 32;
   float* dev = nullptr;
   HIP_CHECK(hipMalloc(&dev, nfloat * sizeof(float)));
@@ -532,38 +770,7 @@ void run_mfma(const Options& o, int compute_units, Report* rep) {
   HIP_CHECK(hipMemcpy(host.data(), dev, nfloat * sizeof(float),
                       hipMemcpyDeviceToHost));
   HIP_CHECK(hipFree(dev));
-
-  using gpucheck::kMfmaK;
-  std::vector<int> a(32 * kMfmaK), bt(32 * kMfmaK);
-  rep->mfma_waves = nwaves;
-  for (long w = 0; w < nwaves; ++w) {
-    const uint64_t key_a = gpucheck::mfma_key(o.seed, static_cast<uint32_t>(w), 0);
-    const uint64_t key_b = gpucheck::mfma_key(o.seed, static_cast<uint32_t>(w), 1);
-    for (int r = 0; r < 32; ++r)
-      for (int k = 0; k < kMfmaK; ++k) {
-        a[r * kMfmaK + k] = gpucheck::mfma_a(key_a, r, k);
-        bt[r * kMfmaK + k] = gpucheck::mfma_b(key_b, k, r);  // B transposed
-      }
-    const float* tile = host.data() + static_cast<size_t>(w) * 32 * 32;
-    bool bad = false;
-    for (int row = 0; row < 32 && !bad; ++row)
-      for (int col = 0; col < 32; ++col) {
-        int sum = 0;
-        for (int k = 0; k < kMfmaK; ++k)
-          sum += a[row * kMfmaK + k] * bt[col * kMfmaK + k];
-        // Every value is an integer of magnitude <= 1152, so equality of
-        // the floats is bit-exactness (NaN compares unequal and is caught).
-        if (!(tile[row * 32 + col] == static_cast<float>(sum))) {
-          bad = true;
-          break;
-        }
-      }
-    if (bad) {
-      if (rep->mfma_bad_waves == 0) rep->mfma_first_bad_wave = w;
-      ++rep->mfma_bad_waves;
-    }
-  }
-  rep->mfma = rep->mfma_bad_waves ? "fail" : "pass";
+  judge_mfma(host, nwaves, o, rep);
 }
 
 // ------------------------------------------------------------------- JSON
@@ -592,6 +799,7 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
     failed += "\"";
   };
   if (hbm_fail) add_failed("hbm");
+  if (!strcmp(r.copy, "fail")) add_failed("copy");
   if (!strcmp(r.mfma, "fail")) add_failed("mfma");
   if (!strcmp(r.bandwidth, "fail")) add_failed("bandwidth");
 
@@ -623,6 +831,14 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
          "\"cache_resident\":%s,",
          r.bandwidth, r.copy_gbs, o.min_copy_gbs,
          o.bytes < kCacheResidentBelow ? "true" : "false");
+  printf("\"copy\":\"%s\",\"copy_mismatch_vectors\":%llu,", r.copy,
+         static_cast<unsigned long long>(r.copy_mismatch_vectors));
+  if (r.have_copy_first_bad)
+    printf("\"copy_first_bad_offset\":%llu,\"copy_first_bad_xor\":\"%s\",",
+           static_cast<unsigned long long>(r.copy_first_bad_offset),
+           hex128(r.copy_first_bad_xor).c_str());
+  else
+    printf("\"copy_first_bad_offset\":null,\"copy_first_bad_xor\":null,");
   printf("\"mfma\":\"%s\",\"mfma_waves\":%ld,\"mfma_bad_waves\":%ld,"
          "\"mfma_first_bad_wave\":%ld,",
          r.mfma, r.mfma_waves, r.mfma_bad_waves, r.mfma_first_bad_wave);
@@ -631,6 +847,24 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
     for (size_t i = 0; i < r.pattern_dump.size(); ++i)
       printf("%s\"%s\"", i ? "," : "", r.pattern_dump[i].c_str());
     printf("],");
+  }
+  if (!o.dump_vectors.empty()) {
+    printf("\"vector_dump\":[");
+    for (size_t i = 0; i < r.vector_dump.size(); ++i)
+      printf("%s{\"index\":%zu,\"pass\":%u,\"value\":\"%s\"}", i ? "," : "",
+             r.vector_dump[i].index, r.vector_dump[i].pass,
+             r.vector_dump[i].value.c_str());
+    printf("],");
+  }
+  if (o.dump_mfma_tile >= 0) {
+    if (r.mfma_tile_valid) {
+      printf("\"mfma_tile\":{\"wave\":%ld,\"values\":[", o.dump_mfma_tile);
+      for (size_t i = 0; i < r.mfma_tile.size(); ++i)
+        printf("%s%d", i ? "," : "", r.mfma_tile[i]);
+      printf("]},");
+    } else {
+      printf("\"mfma_tile\":null,");
+    }
   }
   printf("\"wall_s\":%.4f}\n", wall_s);
   fflush(stdout);
@@ -646,12 +880,15 @@ int main(int argc, char** argv) {
   Report rep;
   try {
     if (o.cpu) {
+      const long nwaves = o.mfma_waves > 0 ? o.mfma_waves : 0;
+      if (int rc = check_mfma_args(o, nwaves)) return rc;
       CpuBackend be(o);
       if (be.mem == nullptr) {
         fprintf(stderr, "gpucheck: cannot allocate %zu bytes\n", o.bytes);
         return 2;
       }
       run_hbm(be, o, &rep);
+      if (nwaves > 0) run_mfma_cpu(o, nwaves, &rep);
     } else {
       int count = 0;
       HIP_CHECK(hipGetDeviceCount(&count));
@@ -661,12 +898,15 @@ int main(int argc, char** argv) {
       HIP_CHECK(hipGetDeviceProperties(&prop, 0));
       rep.device = std::string(prop.name) + " " + prop.gcnArchName;
       rep.compute_units = prop.multiProcessorCount;
+      const long nwaves =
+          o.mfma_waves > 0 ? o.mfma_waves : 8L * prop.multiProcessorCount;
+      if (int rc = check_mfma_args(o, nwaves)) return rc;
       {
         GpuBackend be(o);
         run_hbm(be, o, &rep);
         run_copy(be, o, &rep);
       }
-      run_mfma(o, prop.multiProcessorCount, &rep);
+      run_mfma(o, nwaves, &rep);
     }
   } catch (const HipError& e) {
     fprintf(stderr, "gpucheck: %s\n", e.what.c_str());
@@ -679,6 +919,7 @@ int main(int argc, char** argv) {
 
   int code = 0;
   if (rep.mismatch_vectors != 0) code = 20;
+  else if (!strcmp(rep.copy, "fail")) code = 23;
   else if (!strcmp(rep.mfma, "fail")) code = 21;
   else if (!strcmp(rep.bandwidth, "fail")) code = 22;
   const double wall_s =

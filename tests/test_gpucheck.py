@@ -19,6 +19,7 @@ from k8s_runpod_kubelet_amd.gpu.binder import Binder, BindRequest, PlacementErro
 from k8s_runpod_kubelet_amd.gpu.diagnostics import (
     DiagnosticsManager, GpuBusyError, GpuCheckResult, UnknownGpuError,
     run_gpucheck)
+from tests import gpucheck_reference as ref
 from tests.conftest import wait_until
 
 
@@ -132,6 +133,178 @@ def test_bad_flags_exit_2(gpucheck, args):
     assert "usage:" in proc.stderr
 
 
+@pytest.mark.parametrize("args", [
+    ["--bytes", "64", "--dump-vectors", "4"],          # 4 vectors: 0..3
+    ["--bytes", "64", "--dump-vectors", "0,,1"],
+    ["--bytes", "4096", "--dump-vectors", ",".join(map(str, range(17)))],
+    ["--store-variant", "fast"],
+    ["--passes", "2", "--inject-pass", "2"],
+    ["--bytes", "4096"] + ["--inject-flip", "0:0"] * 17,
+    ["--bytes", "64", "--inject-copy-flip", "31:0"],   # source half
+    ["--bytes", "80", "--inject-copy-flip", "64:0"],   # the odd vector out
+    ["--bytes", "16", "--inject-copy-flip", "0:0"],    # no halves at all
+    ["--mfma-waves", "5", "--inject-mfma", "5:0"],
+    ["--mfma-waves", "5", "--inject-mfma", "0:1024"],
+    ["--mfma-waves", "5"] + ["--inject-mfma", "0:0"] * 9,
+    ["--mfma-waves", "5", "--dump-mfma-tile", "5"],
+    ["--dump-mfma-tile", "0"],                         # --cpu runs no wave
+    ["--inject-mfma", "0:0"],
+])
+def test_bad_test_flags_exit_2(gpucheck, args):
+    proc = subprocess.run([gpucheck, "--cpu", *args], capture_output=True,
+                          text=True, timeout=60)
+    assert proc.returncode == 2
+    assert "usage:" in proc.stderr
+    assert proc.stdout == ""
+
+
+# ------------------------------------------- against the Python reference
+
+OTHER_SEED = 0x0123456789ABCDEF
+
+
+@pytest.mark.parametrize("seed", [ref.DEFAULT_SEED, OTHER_SEED])
+@pytest.mark.parametrize("base", [0, 2**32 - 1, 2**40])
+def test_cpu_pattern_matches_reference(gpucheck, base, seed):
+    """Pins gpucheck_pattern.h to the independent port: the host's expected
+    values (pattern_dump, pass 0) and what the region holds after an even and
+    an odd last pass (vector_dump)."""
+    for passes in (1, 2):
+        rc, out = run_cpu(gpucheck, "--bytes", 64, "--base-index", base,
+                          "--seed", seed, "--passes", passes,
+                          "--dump-pattern", "--dump-vectors", "0,1,2,3")
+        assert rc == 0 and out["seed"] == seed and out["base_index"] == base
+        assert out["pattern_dump"] == [ref.pattern(seed, 0, base + i)
+                                       for i in range(4)]
+        assert out["vector_dump"] == [
+            {"index": i, "pass": passes - 1,
+             "value": ref.pattern(seed, passes - 1, base + i)}
+            for i in range(4)]
+
+
+def test_reference_odd_pass_is_complement_and_passes_differ():
+    """The reference itself: pass 1 complements pass 0, pass 2 is a new
+    pattern, and the index is used at its full 64 bits."""
+    seed = ref.DEFAULT_SEED
+    full = (1 << 128) - 1
+    assert ref.pattern_int(seed, 1, 7) == ref.pattern_int(seed, 0, 7) ^ full
+    assert ref.pattern_int(seed, 3, 7) == ref.pattern_int(seed, 2, 7) ^ full
+    assert ref.pattern_int(seed, 2, 7) != ref.pattern_int(seed, 0, 7)
+    assert ref.pattern_int(seed, 0, 2**32) != ref.pattern_int(seed, 0, 0)
+    assert len(ref.pattern(seed, 0, 0)) == 32
+
+
+def test_cpu_dump_vectors_shows_memory_not_expectation(gpucheck):
+    """A flip in the last pass is visible in vector_dump (what the region
+    holds) and absent from pattern_dump (what the host expects)."""
+    rc, out = run_cpu(gpucheck, "--bytes", 64, "--passes", 1,
+                      "--inject-flip", "17:2", "--dump-pattern",
+                      "--dump-vectors", "1,0")
+    assert rc == 20
+    want1 = ref.pattern_int(ref.DEFAULT_SEED, 0, 1)
+    assert out["pattern_dump"][1] == f"{want1:032x}"
+    assert [d["index"] for d in out["vector_dump"]] == [1, 0]
+    assert int(out["vector_dump"][0]["value"], 16) == want1 ^ (1 << 10)
+    assert out["vector_dump"][1]["value"] == \
+        ref.pattern(ref.DEFAULT_SEED, 0, 0)
+
+
+@pytest.mark.parametrize("variant", ["plain", "nontemporal"])
+def test_cpu_forced_store_variant_is_reported(gpucheck, variant):
+    rc, out = run_cpu(gpucheck, "--bytes", 4096, "--store-variant", variant)
+    assert rc == 0 and out["store_variant"] == variant
+    other = "nontemporal" if variant == "plain" else "plain"
+    assert out[f"write_gbs_{other}"] == 0
+    rc, out = run_cpu(gpucheck, "--bytes", 4096, "--store-variant", "auto")
+    assert rc == 0 and out["store_variant"] == "plain"
+
+
+# The multi-flip cases the GPU suite runs through hbm_verify's reduction
+# (tests/test_gpucheck_gpu.py); here the host loops are held to the same
+# answers.
+
+@pytest.mark.parametrize("case", sorted(ref.MULTI_FLIP_CASES))
+def test_cpu_multiple_flips_count_and_minimum(gpucheck, case):
+    flips = ref.MULTI_FLIP_CASES[case]
+    rc, out = run_cpu(gpucheck, "--bytes", ref.MULTI_FLIP_REGION,
+                      *ref.flip_args(flips))
+    assert rc == 20
+    ref.expect_flips(out, flips)
+    if case == "seven-descending":
+        assert out["mismatch_vectors"] == 6
+
+
+def test_cpu_flip_on_a_complement_pass(gpucheck):
+    flips = [(16 * 300 + 4, 5)]
+    rc, out = run_cpu(gpucheck, "--bytes", 16 * 1024, "--passes", 3,
+                      "--inject-pass", 1, *ref.flip_args(flips),
+                      "--dump-vectors", "300")
+    assert rc == 20
+    ref.expect_flips(out, flips, pass_=1)
+    # pass 2 rewrote the vector: the flip is gone from memory
+    assert out["vector_dump"][0] == {
+        "index": 300, "pass": 2,
+        "value": ref.pattern(ref.DEFAULT_SEED, 2, 300)}
+
+
+def test_cpu_counts_add_across_passes(gpucheck):
+    rc, out = run_cpu(gpucheck, "--bytes", 16 * 1024, "--passes", 2,
+                      "--inject-flip", "4100:3")
+    assert rc == 20
+    assert out["mismatch_vectors"] == 1 and out["first_bad_pass"] == 0
+
+
+# --------------------------------------------------- MFMA checker, --cpu
+
+def test_reference_tile_is_a_product_of_small_integers():
+    tile = ref.mfma_tile(ref.DEFAULT_SEED, 4)
+    assert tile.shape == (32, 32) and tile.dtype == "int64"
+    assert abs(tile).max() <= 147  # far below 2**24: float32 holds it exactly
+    key_a = ref.mfma_key(ref.DEFAULT_SEED, 4, 0)
+    key_b = ref.mfma_key(ref.DEFAULT_SEED, 4, 1)
+    assert tile[31, 0] == sum(
+        ref.mfma_a(key_a, 31, k) * ref.mfma_b(key_b, k, 0)
+        for k in range(ref.MFMA_K))
+    assert (tile != tile.T).any()
+
+
+def test_cpu_mfma_clean_five_waves(gpucheck):
+    rc, out = run_cpu(gpucheck, "--bytes", 4096, "--mfma-waves", 5)
+    assert rc == 0 and out["failed_stages"] == []
+    assert out["mfma"] == "pass" and out["mfma_waves"] == 5
+    assert out["mfma_bad_waves"] == 0 and out["mfma_first_bad_wave"] == -1
+    assert "mfma_tile" not in out
+
+
+@pytest.mark.parametrize("injections,bad,first", ref.MFMA_INJECT_CASES)
+def test_cpu_mfma_injection_is_caught(gpucheck, injections, bad, first):
+    rc, out = run_cpu(gpucheck, "--bytes", 4096, "--mfma-waves", 5,
+                      *ref.mfma_inject_args(injections))
+    assert rc == 21
+    assert out["ok"] is False and out["failed_stages"] == ["mfma"]
+    assert out["mfma"] == "fail" and out["mfma_waves"] == 5
+    assert out["mfma_bad_waves"] == bad
+    assert out["mfma_first_bad_wave"] == first
+    assert out["hbm"] == "pass"
+
+
+def test_cpu_hbm_mismatch_outranks_mfma(gpucheck):
+    rc, out = run_cpu(gpucheck, "--bytes", 4096, "--passes", 1,
+                      "--mfma-waves", 2, "--inject-flip", "0:0",
+                      "--inject-mfma", "1:0")
+    assert rc == 20 and out["failed_stages"] == ["hbm", "mfma"]
+
+
+@pytest.mark.parametrize("seed", [ref.DEFAULT_SEED, OTHER_SEED])
+def test_cpu_mfma_tile_matches_reference(gpucheck, seed):
+    rc, out = run_cpu(gpucheck, "--bytes", 4096, "--mfma-waves", 5,
+                      "--seed", seed, "--dump-mfma-tile", 4)
+    assert rc == 0
+    assert out["mfma_tile"]["wave"] == 4
+    assert out["mfma_tile"]["values"] == \
+        ref.mfma_tile(seed, 4).reshape(-1).tolist()
+
+
 # ------------------------------------------------------------------ runner
 
 GOOD_JSON = {"tool": "gpucheck", "ok": True, "exit_code": 0,
@@ -177,6 +350,15 @@ def test_runner_fail_exit_20(tmp_path, inventory):
     res = run_gpucheck(0, inventory, nbytes=4096, timeout_s=10, binary=stub)
     assert not res.ok and res.exit_code == 20 and res.reason == "hbm"
     assert res.data["first_bad_offset"] == 4096
+
+
+def test_runner_fail_exit_23(tmp_path, inventory):
+    bad = dict(GOOD_JSON, ok=False, exit_code=23, copy_mismatch_vectors=1,
+               copy_first_bad_offset=8192, failed_stages=["copy"])
+    stub = write_stub(tmp_path, "bad", f"echo '{json.dumps(bad)}'\nexit 23\n")
+    res = run_gpucheck(0, inventory, nbytes=4096, timeout_s=10, binary=stub)
+    assert not res.ok and res.exit_code == 23 and res.reason == "copy"
+    assert res.data["copy_first_bad_offset"] == 8192
 
 
 def test_runner_timeout_kills_the_group(tmp_path, inventory):
