@@ -77,12 +77,33 @@ def build_parser() -> argparse.ArgumentParser:
                         "(GB/s; 0 = off)")
     p.add_argument("--gpu-check-parallel", type=int, default=None,
                    help="checks running at once (default 2)")
+    p.add_argument("--no-gpu-check-mx", dest="gpu_check_mx",
+                   action="store_false", default=None,
+                   help="skip the block-scaled MX (FP8/BF8/FP4) stage")
+    p.add_argument("--gpu-check-min-mx-tflops", action="append", default=None,
+                   metavar="FORMAT:X",
+                   help="fail a check whose MX rate for FORMAT (fp8, bf8, "
+                        "fp4, fp8xfp4) is below X TFLOP/s; repeatable")
     p.add_argument("--fake-apiserver", action="store_true",
                    help="start an in-process fake Kubernetes apiserver and "
                         "connect to it (self-contained demo; no cluster "
                         "needed — create pods with curl/kubectl against the "
                         "printed URL)")
     return p
+
+
+def parse_mx_floors(values, base=None) -> dict:
+    """["fp4:4000", ...] laid over ``base`` -> {format: TFLOP/s floor}."""
+    from .gpu.diagnostics import MX_FORMATS
+
+    floors = dict(base or {})
+    for value in values:
+        name, sep, floor = value.partition(":")
+        if not sep or name not in MX_FORMATS:
+            raise SystemExit(f"--gpu-check-min-mx-tflops {value!r}: expected "
+                             f"FORMAT:X with FORMAT one of {list(MX_FORMATS)}")
+        floors[name] = float(floor)
+    return floors
 
 
 def validate_environment() -> None:
@@ -137,6 +158,11 @@ def main(argv=None) -> int:
         cfg.gpu_check_min_copy_gbs = args.gpu_check_min_copy_gbs
     if args.gpu_check_parallel is not None:
         cfg.gpu_check_parallel = args.gpu_check_parallel
+    if args.gpu_check_mx is not None:
+        cfg.gpu_check_mx = args.gpu_check_mx
+    if args.gpu_check_min_mx_tflops is not None:
+        cfg.gpu_check_min_mx_tflops = parse_mx_floors(
+            args.gpu_check_min_mx_tflops, cfg.gpu_check_min_mx_tflops)
 
     validate_environment()
     fake_srv = None

@@ -19,7 +19,7 @@ from __future__ import annotations
 import dataclasses
 import os
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import yaml
 
@@ -119,7 +119,7 @@ class Config:
     evict_on_gpu_failure: bool = True
 
     # Active GPU self-test (gpu/diagnostics.py: HBM pattern, copy bandwidth,
-    # MFMA). Off by default; a failed check fences the GPU until an operator
+    # MFMA, block-scaled MX). Off by default; a failed check fences the GPU until an operator
     # re-check passes.
     gpu_check_on_start: bool = False       # check idle GPUs before serving
     gpu_check_interval_s: float = 0.0      # periodic re-check; 0 = off
@@ -127,6 +127,9 @@ class Config:
     gpu_check_timeout_s: float = 60.0
     gpu_check_min_copy_gbs: float = 0.0    # copy-bandwidth floor; 0 = off
     gpu_check_parallel: int = 2            # checks running at once
+    gpu_check_mx: bool = True              # run the MX (FP8/BF8/FP4) stage
+    # MX rate floors in TFLOP/s by format (fp8, bf8, fp4, fp8xfp4); empty = off
+    gpu_check_min_mx_tflops: Dict[str, float] = field(default_factory=dict)
 
     # GPU inventory overrides (mostly for tests / CPU-only dev)
     gpu_count_override: int = -1
@@ -157,6 +160,11 @@ def load_config(path: Optional[str]) -> Config:
         if norm not in names:
             raise ValueError(f"provider config {path!r}: unknown key {key!r}")
         setattr(cfg, norm, value)
+    if cfg.gpu_check_min_mx_tflops is None:
+        cfg.gpu_check_min_mx_tflops = {}
+    if not isinstance(cfg.gpu_check_min_mx_tflops, dict):
+        raise ValueError(f"provider config {path!r}: gpu_check_min_mx_tflops "
+                         f"must map a format to a floor")
     if cfg.datacenter_ids is None:
         cfg.datacenter_ids = []
     if isinstance(cfg.datacenter_ids, str):

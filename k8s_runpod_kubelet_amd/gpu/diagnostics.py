@@ -3,8 +3,9 @@
 The passive health signal (sysfs/RAS, ``Inventory.refresh_dynamic``) cannot
 see a GPU that still enumerates but no longer stores bits or multiplies
 matrices. ``gpucheck`` (ops/gpucheck/gpucheck.hip) runs real work on an idle
-GPU — an HBM pattern fill/verify, a copy-bandwidth measurement and an exact
-MFMA self-test — and this module turns its verdict into the per-GPU
+GPU — an HBM pattern fill/verify, a copy-bandwidth measurement, an exact
+MFMA self-test and an exact self-test of the block-scaled MX (FP8/BF8/FP4)
+matrix path — and this module turns its verdict into the per-GPU
 schedulability gate.
 
 The binary always runs as a fresh child process scoped to one GPU, exactly
@@ -32,7 +33,8 @@ log = logging.getLogger("gpu.diagnostics")
 
 # gpucheck exit codes (ops/gpucheck/gpucheck.hip)
 EXIT_STAGES = {2: "usage", 11: "hip", 20: "hbm", 21: "mfma", 22: "bandwidth",
-               23: "copy"}
+               23: "copy", 24: "mx", 25: "mx_rate"}
+MX_FORMATS = ("fp8", "bf8", "fp4", "fp8xfp4")
 RESERVATION_PREFIX = "amdvk-system/gpucheck-"
 
 
@@ -50,7 +52,8 @@ class GpuCheckResult:
     ok: bool
     exit_code: Optional[int] = None
     # "" on a pass; otherwise the failing stage ("hbm", "copy", "mfma",
-    # "bandwidth", "hip", "usage") or "timeout", "signal N", "bad-output".
+    # "mx", "bandwidth", "mx_rate", "hip", "usage") or "timeout",
+    # "signal N", "bad-output".
     reason: str = ""
     data: Dict[str, Any] = field(default_factory=dict)  # the binary's JSON
     duration_s: float = 0.0
@@ -67,6 +70,34 @@ class GpuCheckResult:
             "timestamp": self.timestamp,
         })
         return out
+
+
+def mx_floor_args(floors) -> List[str]:
+    """{format: TFLOP/s floor} -> ``--min-mx-tflops`` flags, in the binary's
+    format order; floors of 0 are off. Raises ``ValueError`` for an unknown
+    format."""
+    floors = dict(floors or {})
+    unknown = sorted(set(floors) - set(MX_FORMATS))
+    if unknown:
+        raise ValueError(f"unknown MX format(s) {unknown}; "
+                         f"expected {list(MX_FORMATS)}")
+    out: List[str] = []
+    for name in MX_FORMATS:
+        floor = float(floors.get(name) or 0.0)
+        if floor > 0:
+            out += ["--min-mx-tflops", f"{name}:{floor!r}"]
+    return out
+
+
+def first_bad_mx(data: Dict[str, Any]) -> str:
+    """"fp4 wave 17" for the first format with a bad wave in the binary's
+    JSON, or ""."""
+    formats = data.get("mx_formats")
+    if isinstance(formats, dict):
+        for name, got in formats.items():
+            if isinstance(got, dict) and got.get("bad_waves"):
+                return f"{name} wave {got.get('first_bad_wave')}"
+    return ""
 
 
 def _kill_group(proc: subprocess.Popen) -> None:
@@ -172,7 +203,11 @@ class DiagnosticsManager:
 
     def _extra_args(self) -> List[str]:
         floor = float(getattr(self.config, "gpu_check_min_copy_gbs", 0.0) or 0.0)
-        return ["--min-copy-gbs", repr(floor)] if floor > 0 else []
+        args = ["--min-copy-gbs", repr(floor)] if floor > 0 else []
+        if not getattr(self.config, "gpu_check_mx", True):
+            return args + ["--mx-waves", "0"]
+        return args + mx_floor_args(
+            getattr(self.config, "gpu_check_min_mx_tflops", None))
 
     def check(self, idx: int, operator: bool = False) -> GpuCheckResult:
         """Check one idle GPU. Raises ``UnknownGpuError`` / ``GpuBusyError``.
@@ -244,7 +279,9 @@ class DiagnosticsManager:
             return
         node = {"kind": "Node",
                 "metadata": {"name": self.node_name, "namespace": "default"}}
+        where = first_bad_mx(result.data) if result.reason == "mx" else ""
         message = (f"GPU {idx} failed self-test: stage={result.reason} "
+                   + (f"first_bad_mx={where} " if where else "") +
                    f"first_bad_offset={result.data.get('first_bad_offset')} "
                    f"mismatch_vectors={result.data.get('mismatch_vectors')}; "
                    f"GPU fenced until an operator re-check passes")
@@ -348,12 +385,17 @@ def main(argv=None) -> int:
         prog="python -m k8s_runpod_kubelet_amd.gpu.diagnostics",
         description="Run the active GPU self-test on one GPU and print its "
                     "JSON. Exits with the gpucheck exit code (0 pass, 20 HBM, "
-                    "23 copy mismatch, 21 MFMA, 22 bandwidth, 11 HIP "
-                    "error; 1 for a timeout, signal or unparsable output).")
+                    "23 copy mismatch, 21 MFMA, 24 MX mismatch, 22 bandwidth, "
+                    "25 MX rate below its floor, 11 HIP error; 1 for a "
+                    "timeout, signal or unparsable output).")
     p.add_argument("--gpu", type=int, required=True)
     p.add_argument("--bytes", default="1G")
     p.add_argument("--timeout", type=float, default=60.0)
     p.add_argument("--min-copy-gbs", type=float, default=0.0)
+    p.add_argument("--min-mx-tflops", action="append", default=[],
+                   metavar="FORMAT:X",
+                   help="fail if the MX rate of FORMAT (fp8, bf8, fp4, "
+                        "fp8xfp4) is below X TFLOP/s; repeatable")
     p.add_argument("--sysfs-root", default="/sys")
     p.add_argument("extra", nargs="*",
                    help="further gpucheck arguments (after --)")
@@ -367,6 +409,8 @@ def main(argv=None) -> int:
     extra = list(args.extra)
     if args.min_copy_gbs > 0:
         extra += ["--min-copy-gbs", repr(args.min_copy_gbs)]
+    for floor in args.min_mx_tflops:
+        extra += ["--min-mx-tflops", floor]
     result = run_gpucheck(args.gpu, inventory, nbytes=parse_size(args.bytes),
                           timeout_s=args.timeout, extra_args=extra)
     print(json.dumps(result.to_dict(), sort_keys=True))

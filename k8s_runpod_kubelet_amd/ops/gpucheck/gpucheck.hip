@@ -1,30 +1,38 @@
 // gpucheck — active GPU self-test run between tenants.
 //
 // Tests visible device 0 (the caller scopes visibility with
-// ROCR_VISIBLE_DEVICES) in three stages:
+// ROCR_VISIBLE_DEVICES) in four stages:
 //   1. HBM fill + verify with a hashed 16-byte pattern and its complement,
 //   2. device-to-device copy bandwidth, with the copied half verified against
 //      the pattern its source holds,
-//   3. an exact-integer MFMA self-test (bf16 32x32x16, no memory loads).
+//   3. an exact-integer MFMA self-test (bf16 32x32x16, no memory loads),
+//   4. an exact self-test of the block-scaled MX path (scaled 32x32x64 MFMA
+//      with e4m3, e5m2 and e2m1 operands and E8M0 scales, in the format pairs
+//      fp8, bf8, fp4 and fp8xfp4) and its measured rate per format pair.
 // Prints exactly one JSON object as the last stdout line and exits with a
 // stage-specific code (the first that applies, in this order):
 //   0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, 23 copy mismatch,
-//   21 MFMA mismatch, 22 copy bandwidth below --min-copy-gbs.
+//   21 MFMA mismatch, 24 MX mismatch, 22 copy bandwidth below --min-copy-gbs,
+//   25 an MX rate below its --min-mx-tflops.
 // `--cpu` runs the HBM stage as host loops over malloc'ed memory and makes no
 // HIP call, so the CLI, JSON and mismatch localisation are testable without
 // a GPU. With an explicit --mfma-waves it also fills the MFMA tiles with a
-// host integer matmul and runs the same comparison over them.
+// host integer matmul and runs the same comparison over them, and with an
+// explicit --mx-waves it does the same for the MX tiles (rates stay 0 and
+// their floors are ignored).
 //
 // Flags that exist for the test suite: --dump-pattern, --dump-vectors,
 // --store-variant, --inject-flip, --inject-pass, --inject-copy-flip,
-// --dump-mfma-tile, --inject-mfma. The injections flip bits in the region
-// or in the host copy of the MFMA result; they test the checkers.
+// --dump-mfma-tile, --inject-mfma, --dump-mx-tile, --inject-mx. The
+// injections flip bits in the region or change the host copy of the MFMA or
+// MX result; they test the checkers.
 //
 // Build: hipcc --offload-arch=gfx950 -O2 -std=c++17 gpucheck.hip -o gpucheck
 
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -56,6 +64,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kBlock = 256;
 constexpr size_t kMaxGrid = 2048;
@@ -173,6 +182,140 @@ __global__ __launch_bounds__(kBlock) void mfma_selftest(float* __restrict__ out,
   }
 }
 
+// One lane's 32 elements of an MX operand for one 64-wide k-step, packed
+// the way the scaled MFMA reads them (measured on an MI355X with the exact
+// asymmetric data of this test; h = lane >> 5, k counted from the step's
+// first):
+//   e2m1: nibble j = 0..31 of the low four dwords holds k = 32h + j (the
+//         other four dwords are zero);
+//   8-bit types: byte 16c + i (c = 0, 1; i = 0..15) holds k = 32c + 16h + i.
+//         A 32-wide k-block is thus 16-byte chunk c of BOTH lane halves, not
+//         the 32 bytes of one lane.
+// `first` is the hash index of the step's first k and `stride` the step to
+// the next k (1 along a row of A, 32 down a column of B).
+template <int kType, bool kNonZero>
+__device__ inline i32x8 mx_fragment(uint64_t key, uint32_t first,
+                                    uint32_t stride, int h) {
+  constexpr int bits = kType == gpucheck::kMxE2M1 ? 4 : 8;
+  constexpr int per_dword = 32 / bits;
+  i32x8 frag;
+#pragma unroll
+  for (int d = 0; d < 8; ++d) {
+    uint32_t word = 0;
+    if (d < 32 / per_dword) {
+#pragma unroll
+      for (int i = 0; i < per_dword; ++i) {
+        const int j = d * per_dword + i;
+        const int k = bits == 4 ? 32 * h + j : 32 * (j >> 4) + 16 * h + (j & 15);
+        const uint64_t hash = gpucheck::mix64(key + first + k * stride);
+        const uint32_t code =
+            kNonZero ? gpucheck::mx_nonzero_code_from_hash(kType, hash)
+                     : gpucheck::mx_code_from_hash(kType, hash);
+        word |= code << (bits * i);
+      }
+    }
+    frag[d] = static_cast<int>(word);
+  }
+  return frag;
+}
+
+// K-step kStep of the MX self-test. The step index is a template argument
+// because the byte selects (like cbsz and blgp) are immediates.
+template <int kFmt, int kStep>
+__device__ inline f32x16 mx_step(f32x16 acc, uint64_t key_a, uint64_t key_b,
+                                 int r, int h, int scale_a, int scale_b) {
+  constexpr int ta = gpucheck::kMxFormatTable[kFmt].a;
+  constexpr int tb = gpucheck::kMxFormatTable[kFmt].b;
+  const int k0 = 64 * kStep;
+  const i32x8 a = mx_fragment<ta, false>(
+      key_a, static_cast<uint32_t>(r * gpucheck::kMxK + k0), 1, h);
+  const i32x8 b =
+      mx_fragment<tb, false>(key_b, static_cast<uint32_t>(k0 * 32 + r), 32, h);
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+      a, b, acc, ta, tb, kStep, scale_a, kStep, scale_b);
+}
+
+// Each wave computes one 32x32 tile D = (A scaled).(B scaled) with K = 256 in
+// four 32x32x64 block-scaled steps, operands generated in registers, and
+// stores it to out[wave][row][col]. Lane l (r = l & 31, h = l >> 5) holds
+// elements of row r of A and of column r of B; which k they are depends on
+// the element width (mx_fragment). Byte s of the lane's scale register is the
+// E8M0 scale of k-block 2s + h of that row or column, k = 64s + 32h ..
+// 64s + 32h + 31, for every element width, and step s selects byte s. For
+// e2m1 those are the lane's own 32 elements; for 8-bit types they are chunk h
+// of both lanes r and r + 32.
+// The C/D map depends on the shape only, so it is mfma_selftest's.
+template <int kFmt>
+__global__ __launch_bounds__(kBlock) void mx_selftest(float* __restrict__ out,
+                                                      uint32_t nwaves,
+                                                      uint64_t seed) {
+  const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  // Wave-uniform, as in mfma_selftest: EXEC is full at every MFMA.
+  if (wave >= nwaves) return;
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 31;
+  const int h = lane >> 5;
+  const uint64_t key_a = gpucheck::mx_key(seed, wave, kFmt, 0);
+  const uint64_t key_b = gpucheck::mx_key(seed, wave, kFmt, 1);
+  uint32_t scale_a = 0, scale_b = 0;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    scale_a |= gpucheck::mx_scale_byte(key_a, r, 2 * s + h) << (8 * s);
+    scale_b |= gpucheck::mx_scale_byte(key_b, r, 2 * s + h) << (8 * s);
+  }
+  const int sa = static_cast<int>(scale_a), sb = static_cast<int>(scale_b);
+  f32x16 acc;
+  for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
+  acc = mx_step<kFmt, 0>(acc, key_a, key_b, r, h, sa, sb);
+  acc = mx_step<kFmt, 1>(acc, key_a, key_b, r, h, sa, sb);
+  acc = mx_step<kFmt, 2>(acc, key_a, key_b, r, h, sa, sb);
+  acc = mx_step<kFmt, 3>(acc, key_a, key_b, r, h, sa, sb);
+  float* tile = out + static_cast<size_t>(wave) * (32 * 32);
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
+    tile[row * 32 + r] = acc[g];
+  }
+}
+
+// Timed: every wave issues 4 * trips scaled MFMAs of one format over four
+// independent accumulators, from hashed non-zero operands and unit scales,
+// and writes one float per lane to sink[global thread] so the work is live.
+template <int kFmt>
+__global__ __launch_bounds__(kBlock) void mx_rate(float* __restrict__ sink,
+                                                  uint32_t trips,
+                                                  uint64_t seed) {
+  constexpr int ta = gpucheck::kMxFormatTable[kFmt].a;
+  constexpr int tb = gpucheck::kMxFormatTable[kFmt].b;
+  const uint32_t tid = blockIdx.x * kBlock + threadIdx.x;
+  const uint64_t key = gpucheck::mx_key(seed, tid >> 6, kFmt, 0);
+  const uint32_t lane = threadIdx.x & 63;
+  const i32x8 a = mx_fragment<ta, true>(key, lane * 128, 1, 0);
+  const i32x8 b = mx_fragment<tb, true>(key, lane * 128 + 64, 1, 0);
+  const int unit = 0x7F7F7F7F;  // E8M0 127 = 2^0 in every byte
+  f32x16 acc0, acc1, acc2, acc3;
+  // Different starting values: four chains the compiler cannot fold into one.
+  for (int g = 0; g < 16; ++g) {
+    acc0[g] = 0.0f;
+    acc1[g] = 1.0f;
+    acc2[g] = 2.0f;
+    acc3[g] = 3.0f;
+  }
+  for (uint32_t t = 0; t < trips; ++t) {
+    acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc0, ta, tb,
+                                                           0, unit, 0, unit);
+    acc1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc1, ta, tb,
+                                                           0, unit, 0, unit);
+    acc2 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc2, ta, tb,
+                                                           0, unit, 0, unit);
+    acc3 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc3, ta, tb,
+                                                           0, unit, 0, unit);
+  }
+  float sum = 0.0f;
+  for (int g = 0; g < 16; ++g) sum += acc0[g] + acc1[g] + acc2[g] + acc3[g];
+  sink[tid] = sum;
+}
+
 // ---------------------------------------------------------------- options
 
 struct Options {
@@ -200,11 +343,24 @@ struct Options {
     int elem;
   };
   std::vector<MfmaInject> mfma_inject;
+  // MX stage. Formats are indices into gpucheck::kMxFormatTable.
+  long mx_waves = -1;  // -1: 4 x multiProcessorCount, capped by --mfma-waves
+  int dump_mx_format = -1;
+  long dump_mx_wave = -1;
+  struct MxInject {
+    int format;
+    long wave;
+    int elem;
+  };
+  std::vector<MxInject> mx_inject;
+  double min_mx_tflops[gpucheck::kMxFormats] = {0, 0, 0, 0};
+  uint64_t mx_rate_instr = 65536;  // timed MFMAs per wave and launch
 };
 
 constexpr size_t kMaxFlips = 16;
 constexpr size_t kMaxDumpVectors = 16;
 constexpr size_t kMaxMfmaInject = 8;
+constexpr size_t kMaxMxInject = 8;
 const char* const kVariantNames[2] = {"plain", "nontemporal"};
 
 bool parse_u64(const char* s, uint64_t* out, bool allow_suffix) {
@@ -249,15 +405,22 @@ int usage(const char* why, const char* arg) {
           "[--base-index N] [--seed S]\n"
           "                [--min-copy-gbs X] [--mfma-waves W] "
           "[--store-variant plain|nontemporal|auto]\n"
+          "                [--mx-waves W] [--min-mx-tflops FORMAT:X]... "
+          "[--mx-rate-instr N]\n"
+          "                (FORMAT: fp8, bf8, fp4 or fp8xfp4; --mx-waves 0 "
+          "skips the MX stage)\n"
           "       checks of the checkers:\n"
           "                [--dump-pattern] [--dump-vectors I[,J,...]] "
           "[--dump-mfma-tile W]\n"
           "                [--inject-flip OFFSET:BIT]... [--inject-pass P] "
           "[--inject-copy-flip OFFSET:BIT]\n"
-          "                [--inject-mfma WAVE:ELEM]...\n"
+          "                [--inject-mfma WAVE:ELEM]... "
+          "[--dump-mx-tile FORMAT:WAVE]\n"
+          "                [--inject-mx FORMAT:WAVE:ELEM]...\n"
           "exit: 0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, "
           "23 copy mismatch, 21 MFMA mismatch,\n"
-          "      22 copy bandwidth below --min-copy-gbs\n",
+          "      24 MX mismatch, 22 copy bandwidth below --min-copy-gbs, "
+          "25 MX rate below --min-mx-tflops\n",
           why, arg ? " " : "", arg ? arg : "");
   return 2;
 }
@@ -268,6 +431,17 @@ bool parse_pair(const char* v, uint64_t* a, uint64_t* b) {
   return colon != nullptr &&
          parse_u64(std::string(v, colon - v).c_str(), a, false) &&
          parse_u64(colon + 1, b, false);
+}
+
+// "FORMAT:REST": the index of the named MX format, or -1; *rest is REST.
+int parse_mx_format(const char* v, const char** rest) {
+  const char* colon = v ? strchr(v, ':') : nullptr;
+  if (colon == nullptr) return -1;
+  const std::string name(v, colon - v);
+  *rest = colon + 1;
+  for (int f = 0; f < gpucheck::kMxFormats; ++f)
+    if (name == gpucheck::kMxFormatTable[f].name) return f;
+  return -1;
 }
 
 // Returns 0 on success, 2 on a usage error.
@@ -352,6 +526,36 @@ int parse_args(int argc, char** argv, Options* o) {
       if (o->mfma_inject.size() == kMaxMfmaInject)
         return usage("too many", "--inject-mfma");
       o->mfma_inject.push_back({static_cast<long>(u), static_cast<int>(elem)});
+    } else if (a == "--mx-waves") {
+      if (!parse_u64(next(), &u, false) || u > 65536)
+        return usage("bad value for", "--mx-waves");
+      o->mx_waves = static_cast<long>(u);
+    } else if (a == "--dump-mx-tile") {
+      const char* rest = nullptr;
+      const int f = parse_mx_format(next(), &rest);
+      if (f < 0 || !parse_u64(rest, &u, false) || u >= 65536)
+        return usage("bad value for", "--dump-mx-tile");
+      o->dump_mx_format = f;
+      o->dump_mx_wave = static_cast<long>(u);
+    } else if (a == "--inject-mx") {
+      const char* rest = nullptr;
+      uint64_t elem = 0;
+      const int f = parse_mx_format(next(), &rest);
+      if (f < 0 || !parse_pair(rest, &u, &elem) || u >= 65536 ||
+          elem >= 32 * 32)
+        return usage("bad value for", "--inject-mx");
+      if (o->mx_inject.size() == kMaxMxInject)
+        return usage("too many", "--inject-mx");
+      o->mx_inject.push_back({f, static_cast<long>(u), static_cast<int>(elem)});
+    } else if (a == "--min-mx-tflops") {
+      const char* rest = nullptr;
+      const int f = parse_mx_format(next(), &rest);
+      if (f < 0 || !parse_double(rest, &o->min_mx_tflops[f]))
+        return usage("bad value for", "--min-mx-tflops");
+    } else if (a == "--mx-rate-instr") {
+      if (!parse_u64(next(), &u, false) || u == 0 || u > (1ull << 30))
+        return usage("bad value for", "--mx-rate-instr");
+      o->mx_rate_instr = u;
     } else {
       return usage("unknown argument", a.c_str());
     }
@@ -384,6 +588,16 @@ int check_mfma_args(const Options& o, long nwaves) {
   for (const Options::MfmaInject& m : o.mfma_inject)
     if (m.wave >= nwaves)
       return usage("--inject-mfma wave is outside the run", nullptr);
+  return 0;
+}
+
+// The same for the MX flags.
+int check_mx_args(const Options& o, long nwaves) {
+  if (o.dump_mx_wave >= nwaves)
+    return usage("--dump-mx-tile wave is outside the run", nullptr);
+  for (const Options::MxInject& m : o.mx_inject)
+    if (m.wave >= nwaves)
+      return usage("--inject-mx wave is outside the run", nullptr);
   return 0;
 }
 
@@ -421,6 +635,17 @@ struct Report {
   long mfma_waves = 0, mfma_bad_waves = 0, mfma_first_bad_wave = -1;
   bool mfma_tile_valid = false;
   std::vector<int> mfma_tile;
+  // MX
+  const char* mx = "skipped";
+  const char* mx_rate = "skipped";
+  long mx_waves = 0;
+  struct MxFormatResult {
+    long bad_waves = 0, first_bad_wave = -1;
+    double tflops = 0;
+  };
+  MxFormatResult mx_formats[gpucheck::kMxFormats];
+  bool mx_tile_valid = false;
+  std::vector<long> mx_tile;  // values times 16
 };
 
 std::string hex128(const Vec16& v) {
@@ -773,6 +998,231 @@ void run_mfma(const Options& o, long nwaves, Report* rep) {
   judge_mfma(host, nwaves, o, rep);
 }
 
+// Decoders of the MX element and scale codes, from the OCP formulas: sign,
+// exponent field e with its bias, mantissa field m; e = 0 is subnormal.
+double decode_minifloat(uint32_t code, int exp_bits, int mant_bits, int bias) {
+  const uint32_t m = code & ((1u << mant_bits) - 1);
+  const uint32_t e = (code >> mant_bits) & ((1u << exp_bits) - 1);
+  const bool neg = (code >> (exp_bits + mant_bits)) & 1u;
+  const double frac = static_cast<double>(m) / (1u << mant_bits);
+  const double mag = e == 0 ? ldexp(frac, 1 - bias)
+                            : ldexp(1.0 + frac, static_cast<int>(e) - bias);
+  return neg ? -mag : mag;
+}
+
+double decode_e2m1(uint32_t code) { return decode_minifloat(code, 2, 1, 1); }
+
+// e4m3fn: no infinities, and S.1111.111 is the only NaN.
+double decode_e4m3(uint32_t code) {
+  if ((code & 0x7Fu) == 0x7Fu) return NAN;
+  return decode_minifloat(code, 4, 3, 7);
+}
+
+// e5m2: IEEE-like, exponent field 31 is infinity or NaN.
+double decode_e5m2(uint32_t code) {
+  if ((code & 0x7Cu) == 0x7Cu)
+    return (code & 3u) ? NAN : ((code & 0x80u) ? -INFINITY : INFINITY);
+  return decode_minifloat(code, 5, 2, 15);
+}
+
+double decode_e8m0(uint32_t code) {
+  return code == 255 ? NAN : ldexp(1.0, static_cast<int>(code) - 127);
+}
+
+// The 32x32 tile wave `w` must produce in format `f`, times 16, row-major:
+// decode every element and scale, multiply, sum over k. Operands are held
+// times 4 (exact: an element is a multiple of 1/2 and a scale at least 1/2)
+// and every sum is an integer below 2^24, so the float arithmetic is exact;
+// the loop order keeps the inner loop free of a reduction.
+void mx_expected_tile(int f, uint64_t seed, long w, float* out) {
+  using gpucheck::kMxBlock;
+  using gpucheck::kMxK;
+  const gpucheck::MxFormat& fmt = gpucheck::kMxFormatTable[f];
+  const uint64_t key_a = gpucheck::mx_key(seed, static_cast<uint32_t>(w), f, 0);
+  const uint64_t key_b = gpucheck::mx_key(seed, static_cast<uint32_t>(w), f, 1);
+  // Thousands of tiles draw on the same few codes, so each is generated and
+  // decoded once: an element's code depends on kMxHashBits bits of its hash.
+  constexpr uint32_t nhash = 1u << gpucheck::kMxHashBits;
+  static const std::vector<double> table = [] {
+    std::vector<double> t(3 * nhash + 256);
+    for (uint32_t h = 0; h < nhash; ++h) {
+      t[h] = decode_e4m3(gpucheck::mx_code_from_hash(gpucheck::kMxE4M3, h));
+      t[nhash + h] =
+          decode_e5m2(gpucheck::mx_code_from_hash(gpucheck::kMxE5M2, h));
+      t[2 * nhash + h] =
+          decode_e2m1(gpucheck::mx_code_from_hash(gpucheck::kMxE2M1, h));
+    }
+    for (uint32_t c = 0; c < 256; ++c) t[3 * nhash + c] = decode_e8m0(c);
+    return t;
+  }();
+  auto values_of = [&](int type) {
+    return &table[type == gpucheck::kMxE2M1 ? 2 * nhash : nhash * type];
+  };
+  const double* dec_a = values_of(fmt.a);
+  const double* dec_b = values_of(fmt.b);
+  const double* dec_scale = &table[3 * nhash];
+  std::vector<float> a(32 * kMxK), b(kMxK * 32);
+  for (int r = 0; r < 32; ++r)
+    for (int blk = 0; blk < kMxK / kMxBlock; ++blk) {
+      const double sa = dec_scale[gpucheck::mx_scale_byte(key_a, r, blk)];
+      const double sb = dec_scale[gpucheck::mx_scale_byte(key_b, r, blk)];
+      for (int k = blk * kMxBlock; k < (blk + 1) * kMxBlock; ++k) {
+        a[r * kMxK + k] = static_cast<float>(
+            4.0 * sa * dec_a[gpucheck::mx_a_hash(key_a, r, k) & (nhash - 1)]);
+        b[k * 32 + r] = static_cast<float>(
+            4.0 * sb * dec_b[gpucheck::mx_b_hash(key_b, k, r) & (nhash - 1)]);
+      }
+    }
+  for (int row = 0; row < 32; ++row) {
+    float* sums = out + row * 32;
+    for (int col = 0; col < 32; ++col) sums[col] = 0.0f;
+    for (int k = 0; k < kMxK; ++k) {
+      const float av = a[row * kMxK + k];
+      const float* brow = &b[k * 32];
+      for (int col = 0; col < 32; ++col) sums[col] += av * brow[col];
+    }
+  }
+}
+
+// `host` holds the tiles format-major: host[(f * nwaves + w) * 1024 + e].
+float* mx_tile_at(std::vector<float>& host, long nwaves, int f, long w) {
+  return host.data() + (static_cast<size_t>(f) * nwaves + w) * (32 * 32);
+}
+
+// bad[f * nwaves + w] != 0 where that tile differs from the expected product.
+std::vector<char> mx_compare(std::vector<float>& host, long nwaves,
+                             uint64_t seed) {
+  std::vector<char> bad(static_cast<size_t>(gpucheck::kMxFormats) * nwaves, 0);
+  std::vector<float> want(32 * 32);
+  for (int f = 0; f < gpucheck::kMxFormats; ++f)
+    for (long w = 0; w < nwaves; ++w) {
+      mx_expected_tile(f, seed, w, want.data());
+      const float* tile = mx_tile_at(host, nwaves, f, w);
+      // Exact by the bound in gpucheck_pattern.h: == is bit-exactness, and
+      // NaN compares unequal. want holds the value times 16.
+      for (int e = 0; e < 32 * 32; ++e)
+        if (!(tile[e] * 16.0f == want[e])) {
+          bad[static_cast<size_t>(f) * nwaves + w] = 1;
+          break;
+        }
+    }
+  return bad;
+}
+
+// Everything after the tiles are in host memory, as judge_mfma.
+void judge_mx(std::vector<float>& host, long nwaves, const Options& o,
+              Report* rep) {
+  rep->mx_waves = nwaves;
+  bool dump_bad = false;
+  if (o.dump_mx_wave >= 0) {
+    const float* tile = mx_tile_at(host, nwaves, o.dump_mx_format, o.dump_mx_wave);
+    rep->mx_tile_valid = true;
+    for (int e = 0; e < 32 * 32; ++e) {
+      const float v16 = tile[e] * 16.0f;
+      // Not a finite multiple of 1/16 a long can hold: no dump, a bad wave.
+      if (!(v16 >= -1e15f && v16 <= 1e15f) ||
+          v16 != static_cast<float>(static_cast<long>(v16))) {
+        rep->mx_tile_valid = false;
+        rep->mx_tile.clear();
+        dump_bad = true;
+        break;
+      }
+      rep->mx_tile.push_back(static_cast<long>(v16));
+    }
+  }
+  for (const Options::MxInject& m : o.mx_inject)
+    mx_tile_at(host, nwaves, m.format, m.wave)[m.elem] += 1.0f;
+  std::vector<char> bad = mx_compare(host, nwaves, o.seed);
+  if (dump_bad)
+    bad[static_cast<size_t>(o.dump_mx_format) * nwaves + o.dump_mx_wave] = 1;
+  bool any = false;
+  for (int f = 0; f < gpucheck::kMxFormats; ++f) {
+    Report::MxFormatResult& r = rep->mx_formats[f];
+    for (long w = 0; w < nwaves; ++w)
+      if (bad[static_cast<size_t>(f) * nwaves + w]) {
+        if (r.bad_waves == 0) r.first_bad_wave = w;
+        ++r.bad_waves;
+        any = true;
+      }
+  }
+  rep->mx = any ? "fail" : "pass";
+}
+
+// --cpu: the tiles come from the host product, so this exercises the
+// decoders, judge_mx and the JSON, not a device. No rate is measured.
+void run_mx_cpu(const Options& o, long nwaves, Report* rep) {
+  std::vector<float> host(static_cast<size_t>(gpucheck::kMxFormats) * nwaves *
+                          32 * 32);
+  for (int f = 0; f < gpucheck::kMxFormats; ++f)
+    for (long w = 0; w < nwaves; ++w) {
+      float* tile = mx_tile_at(host, nwaves, f, w);
+      mx_expected_tile(f, o.seed, w, tile);
+      for (int e = 0; e < 32 * 32; ++e) tile[e] /= 16.0f;
+    }
+  judge_mx(host, nwaves, o, rep);
+}
+
+template <int kFmt>
+void launch_mx_formats(float* dev, long nwaves, uint64_t seed) {
+  const unsigned int blocks = static_cast<unsigned int>((nwaves + 3) / 4);
+  hipLaunchKernelGGL(mx_selftest<kFmt>, dim3(blocks), dim3(kBlock), 0, 0,
+                     dev + static_cast<size_t>(kFmt) * nwaves * 32 * 32,
+                     static_cast<uint32_t>(nwaves), seed);
+  if constexpr (kFmt + 1 < gpucheck::kMxFormats)
+    launch_mx_formats<kFmt + 1>(dev, nwaves, seed);
+}
+
+// Median of five timed launches after one warm-up, as the copy stage; two
+// workgroups of four waves per compute unit put waves on every SIMD.
+template <int kFmt>
+void time_mx_formats(float* sink, unsigned int blocks, const Options& o,
+                     GpuTimer& timer, Report* rep) {
+  const uint32_t trips = static_cast<uint32_t>((o.mx_rate_instr + 3) / 4);
+  std::vector<double> times;
+  for (int rep_i = 0; rep_i < 6; ++rep_i) {
+    timer.begin();
+    hipLaunchKernelGGL(mx_rate<kFmt>, dim3(blocks), dim3(kBlock), 0, 0, sink,
+                       trips, o.seed);
+    const double s = timer.end();
+    if (rep_i > 0) times.push_back(s);
+  }
+  std::sort(times.begin(), times.end());
+  const double seconds = times[times.size() / 2];
+  const double flop = 2.0 * 32 * 32 * 64 * 4.0 * trips * (blocks * 4.0);
+  rep->mx_formats[kFmt].tflops = seconds > 0 ? flop / seconds / 1e12 : 0.0;
+  if constexpr (kFmt + 1 < gpucheck::kMxFormats)
+    time_mx_formats<kFmt + 1>(sink, blocks, o, timer, rep);
+}
+
+void run_mx(const Options& o, long nwaves, int compute_units, Report* rep) {
+  const size_t nfloat =
+      static_cast<size_t>(gpucheck::kMxFormats) * nwaves * 32 * 32;
+  float* dev = nullptr;
+  HIP_CHECK(hipMalloc(&dev, nfloat * sizeof(float)));
+  HIP_CHECK(hipMemset(dev, 0xFF, nfloat * sizeof(float)));
+  launch_mx_formats<0>(dev, nwaves, o.seed);
+  HIP_CHECK(hipGetLastError());
+  std::vector<float> host(nfloat);
+  HIP_CHECK(hipMemcpy(host.data(), dev, nfloat * sizeof(float),
+                      hipMemcpyDeviceToHost));
+  HIP_CHECK(hipFree(dev));
+  judge_mx(host, nwaves, o, rep);
+
+  const unsigned int blocks =
+      static_cast<unsigned int>(2 * std::max(1, compute_units));
+  float* sink = nullptr;
+  HIP_CHECK(hipMalloc(&sink, static_cast<size_t>(blocks) * kBlock * sizeof(float)));
+  GpuTimer timer;
+  timer.init();
+  time_mx_formats<0>(sink, blocks, o, timer, rep);
+  HIP_CHECK(hipFree(sink));
+  rep->mx_rate = "pass";
+  for (int f = 0; f < gpucheck::kMxFormats; ++f)
+    if (o.min_mx_tflops[f] > 0 &&
+        rep->mx_formats[f].tflops < o.min_mx_tflops[f])
+      rep->mx_rate = "fail";
+}
+
 // ------------------------------------------------------------------- JSON
 
 std::string json_escape(const std::string& s) {
@@ -801,7 +1251,9 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
   if (hbm_fail) add_failed("hbm");
   if (!strcmp(r.copy, "fail")) add_failed("copy");
   if (!strcmp(r.mfma, "fail")) add_failed("mfma");
+  if (!strcmp(r.mx, "fail")) add_failed("mx");
   if (!strcmp(r.bandwidth, "fail")) add_failed("bandwidth");
+  if (!strcmp(r.mx_rate, "fail")) add_failed("mx_rate");
 
   printf("{\"tool\":\"gpucheck\",\"mode\":\"%s\",\"device\":\"%s\","
          "\"compute_units\":%d,\"ok\":%s,\"exit_code\":%d,"
@@ -866,6 +1318,26 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
       printf("\"mfma_tile\":null,");
     }
   }
+  printf("\"mx\":\"%s\",\"mx_waves\":%ld,\"mx_rate\":\"%s\",\"mx_formats\":{",
+         r.mx, r.mx_waves, r.mx_rate);
+  for (int f = 0; f < gpucheck::kMxFormats; ++f)
+    printf("%s\"%s\":{\"bad_waves\":%ld,\"first_bad_wave\":%ld,"
+           "\"tflops\":%.3f}",
+           f ? "," : "", gpucheck::kMxFormatTable[f].name,
+           r.mx_formats[f].bad_waves, r.mx_formats[f].first_bad_wave,
+           r.mx_formats[f].tflops);
+  printf("},");
+  if (o.dump_mx_wave >= 0) {
+    if (r.mx_tile_valid) {
+      printf("\"mx_tile\":{\"format\":\"%s\",\"wave\":%ld,\"values_x16\":[",
+             gpucheck::kMxFormatTable[o.dump_mx_format].name, o.dump_mx_wave);
+      for (size_t i = 0; i < r.mx_tile.size(); ++i)
+        printf("%s%ld", i ? "," : "", r.mx_tile[i]);
+      printf("]},");
+    } else {
+      printf("\"mx_tile\":null,");
+    }
+  }
   printf("\"wall_s\":%.4f}\n", wall_s);
   fflush(stdout);
 }
@@ -882,6 +1354,8 @@ int main(int argc, char** argv) {
     if (o.cpu) {
       const long nwaves = o.mfma_waves > 0 ? o.mfma_waves : 0;
       if (int rc = check_mfma_args(o, nwaves)) return rc;
+      const long mx_waves = o.mx_waves > 0 ? o.mx_waves : 0;
+      if (int rc = check_mx_args(o, mx_waves)) return rc;
       CpuBackend be(o);
       if (be.mem == nullptr) {
         fprintf(stderr, "gpucheck: cannot allocate %zu bytes\n", o.bytes);
@@ -889,6 +1363,7 @@ int main(int argc, char** argv) {
       }
       run_hbm(be, o, &rep);
       if (nwaves > 0) run_mfma_cpu(o, nwaves, &rep);
+      if (mx_waves > 0) run_mx_cpu(o, mx_waves, &rep);
     } else {
       int count = 0;
       HIP_CHECK(hipGetDeviceCount(&count));
@@ -901,12 +1376,20 @@ int main(int argc, char** argv) {
       const long nwaves =
           o.mfma_waves > 0 ? o.mfma_waves : 8L * prop.multiProcessorCount;
       if (int rc = check_mfma_args(o, nwaves)) return rc;
+      // An explicit --mfma-waves caps the default, so a small run stays small.
+      long mx_waves = o.mx_waves;
+      if (mx_waves < 0) {
+        mx_waves = 4L * prop.multiProcessorCount;
+        if (o.mfma_waves > 0) mx_waves = std::min(mx_waves, o.mfma_waves);
+      }
+      if (int rc = check_mx_args(o, mx_waves)) return rc;
       {
         GpuBackend be(o);
         run_hbm(be, o, &rep);
         run_copy(be, o, &rep);
       }
       run_mfma(o, nwaves, &rep);
+      if (mx_waves > 0) run_mx(o, mx_waves, prop.multiProcessorCount, &rep);
     }
   } catch (const HipError& e) {
     fprintf(stderr, "gpucheck: %s\n", e.what.c_str());
@@ -921,7 +1404,9 @@ int main(int argc, char** argv) {
   if (rep.mismatch_vectors != 0) code = 20;
   else if (!strcmp(rep.copy, "fail")) code = 23;
   else if (!strcmp(rep.mfma, "fail")) code = 21;
+  else if (!strcmp(rep.mx, "fail")) code = 24;
   else if (!strcmp(rep.bandwidth, "fail")) code = 22;
+  else if (!strcmp(rep.mx_rate, "fail")) code = 25;
   const double wall_s =
       std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   print_report(o, rep, code, wall_s);

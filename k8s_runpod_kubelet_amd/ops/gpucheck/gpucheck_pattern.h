@@ -74,4 +74,94 @@ GPUCHECK_HD inline uint16_t bf16_bits_small_int(int v) {
   return static_cast<uint16_t>(mag | (v < 0 ? 0x8000 : 0));
 }
 
+// MX self-test: block-scaled FP8/BF8/FP4 operands for the 32x32x64 scaled
+// MFMA. A is [32][256] row-major, B is [256][32] row-major, and every 32-wide
+// k-block of a row of A (column of B) carries one E8M0 scale.
+//
+// Exactness. Element magnitudes are at most 7.5 (e4m3: m/2, m <= 15), 3.5
+// (e5m2: m/2, m <= 7) and 6 (e2m1); all are multiples of 1/2. Scales are
+// 2^-1, 1 and 2. A scaled product a.sa.b.sb is therefore a multiple of
+// (1/2)^4 = 2^-4 of magnitude at most 7.5^2 . 4 = 225, and the magnitudes of
+// the K = 256 products of one output sum to at most 256 . 225 = 57600. In
+// units of 2^-4 that is 57600 . 16 = 921600 < 2^24, so every partial sum, in
+// any order and grouping, is an integer below 2^24 in those units and exact in
+// f32: the device result has one correct value and the host compares with ==.
+constexpr int kMxK = 256;  // 4 chained 32x32x64 steps
+constexpr int kMxBlock = 32;
+constexpr int kMxFormats = 4;
+
+// Element types, numbered as the instruction's cbsz/blgp fields number them.
+constexpr int kMxE4M3 = 0;
+constexpr int kMxE5M2 = 1;
+constexpr int kMxE2M1 = 4;
+
+struct MxFormat {
+  const char* name;
+  int a;  // element type of A
+  int b;  // element type of B
+};
+constexpr MxFormat kMxFormatTable[kMxFormats] = {
+    {"fp8", kMxE4M3, kMxE4M3},
+    {"bf8", kMxE5M2, kMxE5M2},
+    {"fp4", kMxE2M1, kMxE2M1},
+    {"fp8xfp4", kMxE4M3, kMxE2M1},
+};
+
+// Bit 40 keeps these keys apart from mfma_key's (wave << 1 | which).
+GPUCHECK_HD inline uint64_t mx_key(uint64_t seed, uint32_t wave,
+                                   uint32_t format, uint32_t which) {
+  return mix64(seed ^ mix64((1ull << 40) | (static_cast<uint64_t>(wave) << 3) |
+                            (format << 1) | which));
+}
+
+// Bits of +m/2 in a format with `mant` mantissa bits and exponent bias
+// `bias`, for 0 <= m < 2^(mant+1): m = 2^e . (1 + f) gives the exponent
+// field e - 1 + bias and the fraction f in the top bits of the mantissa.
+GPUCHECK_HD inline uint32_t mx_half_steps_bits(uint32_t m, int mant, int bias) {
+  if (m == 0) return 0;
+  int e = 0;
+  while ((m >> (e + 1)) != 0) ++e;
+  return (static_cast<uint32_t>(e - 1 + bias) << mant) |
+         ((m - (1u << e)) << (mant - e));
+}
+
+// The code of one element from its hash: e2m1 takes any of its 16 codes;
+// e4m3 is +-m/2 for m = 0..15 and e5m2 +-m/2 for m = 0..7, sign in bit 7.
+// Only the low kMxHashBits bits of the hash are used.
+constexpr int kMxHashBits = 5;
+GPUCHECK_HD inline uint32_t mx_code_from_hash(int type, uint64_t h) {
+  const uint32_t sign = static_cast<uint32_t>(h >> 4) & 1u;
+  if (type == kMxE2M1) return static_cast<uint32_t>(h) & 15u;
+  if (type == kMxE4M3)
+    return (sign << 7) |
+           mx_half_steps_bits(static_cast<uint32_t>(h) & 15u, 3, 7);
+  return (sign << 7) | mx_half_steps_bits(static_cast<uint32_t>(h) & 7u, 2, 15);
+}
+
+// As above but never +-0 (which becomes +-1): the rate kernels' operands.
+GPUCHECK_HD inline uint32_t mx_nonzero_code_from_hash(int type, uint64_t h) {
+  const uint32_t c = mx_code_from_hash(type, h);
+  if (type == kMxE2M1) return (c & 7u) ? c : (c | 2u);
+  if ((c & 0x7Fu) != 0) return c;
+  return c | (type == kMxE4M3 ? 0x38u : 0x3Cu);
+}
+
+// The hash of A[row][k] and of B[k][col]. B[k][c] and B[c][k] hash different
+// element indices: B is not symmetric.
+GPUCHECK_HD inline uint64_t mx_a_hash(uint64_t key_a, int row, int k) {
+  return mix64(key_a + static_cast<uint32_t>(row * kMxK + k));
+}
+GPUCHECK_HD inline uint64_t mx_b_hash(uint64_t key_b, int k, int col) {
+  return mix64(key_b + static_cast<uint32_t>(k * 32 + col));
+}
+
+// E8M0 scale byte (126, 127 or 128) of k-block `block` (k / 32) of row or
+// column `rc`. The offset keeps the scale indices clear of the 8192 elements.
+GPUCHECK_HD inline uint32_t mx_scale_byte(uint64_t key, int rc, int block) {
+  return 126u + static_cast<uint32_t>(
+                    mix64(key + 0x10000u +
+                          static_cast<uint32_t>(rc * (kMxK / kMxBlock) + block)) %
+                    3u);
+}
+
 }  // namespace gpucheck

@@ -100,6 +100,10 @@ gpu_check_read_gbs = Gauge("amdvk_gpu_check_read_gbs",
 gpu_check_write_gbs = Gauge("amdvk_gpu_check_write_gbs",
                             "Fill-write bandwidth of the last self-test (GB/s)",
                             ["gpu"], registry=registry)
+gpu_check_mx_tflops = Gauge("amdvk_gpu_check_mx_tflops",
+                            "Block-scaled MX MFMA rate of the last self-test "
+                            "(TFLOP/s)",
+                            ["gpu", "format"], registry=registry)
 gpu_check_timestamp = Gauge("amdvk_gpu_check_timestamp_seconds",
                             "Unix time of the last self-test",
                             ["gpu"], registry=registry)
@@ -118,6 +122,12 @@ def observe_gpu_check(index: int, result, verdict_ok: bool) -> None:
         value = result.data.get(key)
         if isinstance(value, (int, float)):
             gauge.labels(label).set(value)
+    formats = result.data.get("mx_formats")
+    if result.data.get("mx_rate") in ("pass", "fail") and isinstance(formats, dict):
+        for name, got in formats.items():
+            value = got.get("tflops") if isinstance(got, dict) else None
+            if isinstance(value, (int, float)):
+                gpu_check_mx_tflops.labels(label, str(name)).set(value)
 
 
 def render() -> bytes:
