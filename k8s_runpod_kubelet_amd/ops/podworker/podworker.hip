@@ -231,8 +231,34 @@ static void publish(hsa_kernel_dispatch_packet_t* p, bool barrier) {
                    __ATOMIC_RELEASE);
 }
 
+// The sample set: every multiple of 4099 in the head window plus the last
+// element — or, for --verify-all, every element. The one place it is built:
+// the run and --dump-sample-set both call this.
+static std::vector<int> sample_set(int n, bool verify_all) {
+  std::vector<int> sample;
+  if (verify_all) {
+    sample.resize(n);
+    for (int i = 0; i < n; ++i) sample[i] = i;
+  } else {
+    const int head = n < (1 << 16) ? n : (1 << 16);
+    for (int i = 0; i < head; i += 4099) sample.push_back(i);
+    sample.push_back(n - 1);
+  }
+  return sample;
+}
+
+static const size_t kMaxInject = 4;            // --inject-store, at most
+static const size_t kMaxDumpSamples = 1 << 17; // --dump-samples, at most
+
+// Tests and measurement only; a pod's run has none of these set.
+struct TestHooks {
+  std::vector<int> inject;    // --inject-store: out[I] = 1 before the gather
+  bool dump_samples = false;  // --dump-samples: print dst before comparing
+};
+
 // Touch every visible device: queue + code object + two dispatches + verify.
-static int touch_gpus(int expect_gpus, int n, bool verify_all, Timing* tm) {
+static int touch_gpus(int expect_gpus, int n, bool verify_all,
+                      const TestHooks& hooks, Timing* tm) {
   double t0 = now_ms();
   HSA_CHECK(hsa_init());
   Agents agents;
@@ -260,18 +286,9 @@ static int touch_gpus(int expect_gpus, int n, bool verify_all, Timing* tm) {
   }
   tm->runtime_init += now_ms() - t0;
 
-  // The sample set: every multiple of 4099 in the head window plus the last
-  // element — or, for --verify-all, every element.
-  std::vector<int> sample;
-  if (verify_all) {
-    sample.resize(n);
-    for (int i = 0; i < n; ++i) sample[i] = i;
-  } else {
-    const int head = n < (1 << 16) ? n : (1 << 16);
-    for (int i = 0; i < head; i += 4099) sample.push_back(i);
-    sample.push_back(n - 1);
-  }
+  const std::vector<int> sample = sample_set(n, verify_all);
   const int m = static_cast<int>(sample.size());
+  const size_t n_inject = hooks.inject.size();
 
   for (int dev = 0; dev < count; ++dev) {
     hsa_agent_t gpu = agents.gpus[dev];
@@ -324,7 +341,13 @@ static int touch_gpus(int expect_gpus, int n, bool verify_all, Timing* tm) {
         reinterpret_cast<void**>(&dst)));
     // one kernarg block for both kernels, each segment 64-byte aligned
     const size_t gather_at = (touch.kernarg_size + 63u) & ~size_t(63);
-    const size_t kernarg_bytes = gather_at + gather.kernarg_size;
+    // --inject-store: one more touch segment per injection, after the gather's
+    const size_t inject_at =
+        (gather_at + gather.kernarg_size + 63u) & ~size_t(63);
+    const size_t inject_stride = (touch.kernarg_size + 63u) & ~size_t(63);
+    const size_t kernarg_bytes =
+        n_inject ? inject_at + n_inject * inject_stride
+                 : gather_at + gather.kernarg_size;
     HSA_CHECK(hsa_amd_memory_pool_allocate(
         kernarg_pool, kernarg_bytes, 0, reinterpret_cast<void**>(&kernarg)));
     HSA_CHECK(hsa_amd_agents_allow_access(1, &gpu, nullptr, idx));
@@ -347,21 +370,35 @@ static int touch_gpus(int expect_gpus, int n, bool verify_all, Timing* tm) {
             static_cast<const int*>(idx));
     put_arg(gather_args, gather, kGatherArgOffsets[2], dst);
     put_arg(gather_args, gather, kGatherArgOffsets[3], m);
+    for (size_t k = 0; k < n_inject; ++k) {
+      // touch_kernel(out + I, 1): its lane 0 stores 2*0+1 into out[I]
+      char* args = kernarg + inject_at + k * inject_stride;
+      put_arg(args, touch, kTouchArgOffsets[0], out + hooks.inject[k]);
+      put_arg(args, touch, kTouchArgOffsets[1], 1);
+    }
 
     // Two packets, one doorbell. Bodies first, each header last with a
     // release store; the gather waits for the touch through its barrier bit.
-    const uint64_t at = hsa_queue_add_write_index_relaxed(queue, 2);
+    // Each --inject-store puts one more touch packet between the two, with
+    // the barrier bit, so it runs after the touch and before the gather.
+    const uint64_t last = 1 + n_inject;  // the gather's place after `at`
+    const uint64_t at = hsa_queue_add_write_index_relaxed(queue, last + 1);
     auto* ring = static_cast<hsa_kernel_dispatch_packet_t*>(queue->base_address);
     const uint32_t mask = queue->size - 1;
     hsa_kernel_dispatch_packet_t* p0 = &ring[at & mask];
-    hsa_kernel_dispatch_packet_t* p1 = &ring[(at + 1) & mask];
+    hsa_kernel_dispatch_packet_t* p1 = &ring[(at + last) & mask];
     fill_dispatch(p0, touch, static_cast<uint32_t>(n), kernarg,
                   hsa_signal_t{0});
+    for (size_t k = 0; k < n_inject; ++k)
+      fill_dispatch(&ring[(at + 1 + k) & mask], touch, 1,
+                    kernarg + inject_at + k * inject_stride, hsa_signal_t{0});
     fill_dispatch(p1, gather, static_cast<uint32_t>(m), gather_args, done);
     publish(p0, false);
+    for (size_t k = 0; k < n_inject; ++k)
+      publish(&ring[(at + 1 + k) & mask], true);
     publish(p1, true);
     hsa_signal_store_screlease(queue->doorbell_signal,
-                               static_cast<hsa_signal_value_t>(at + 1));
+                               static_cast<hsa_signal_value_t>(at + last));
 
     // Bounded wait: 100 ms slices, 10 s in all, no retry.
     const uint64_t slice = ticks_per_s / 10;
@@ -384,6 +421,10 @@ static int touch_gpus(int expect_gpus, int n, bool verify_all, Timing* tm) {
       return 11;
     }
 
+    if (hooks.dump_samples)  // what the gather wrote, never the expectation
+      for (int j = 0; j < m; ++j)
+        printf("podworker: sample dev %d %d %d 0x%08X\n", dev, j, sample[j],
+               dst[j]);
     for (int j = 0; j < m; ++j) {
       const int i = sample[j];
       if (dst[j] != static_cast<unsigned int>(i) * 2u + 1u) {
@@ -448,6 +489,9 @@ int main(int argc, char** argv) {
   std::vector<int> ports;
   long long touch_elems = 1 << 20;  // tests and measurement only
   bool verify_all = false;          // tests and measurement only
+  bool dump_sample_set = false;     // tests and measurement only
+  TestHooks hooks;                  // tests and measurement only
+  std::vector<long long> inject;    // --inject-store, as given
 
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -460,6 +504,9 @@ int main(int argc, char** argv) {
     else if (a == "--listen-port") ports.push_back(atoi(next()));
     else if (a == "--touch-elems") touch_elems = atoll(next());
     else if (a == "--verify-all") verify_all = true;
+    else if (a == "--dump-sample-set") dump_sample_set = true;
+    else if (a == "--dump-samples") hooks.dump_samples = true;
+    else if (a == "--inject-store") inject.push_back(atoll(next()));
     else if (a == "--fail") {
       fprintf(stderr, "podworker: simulated failure\n");
       finish(1);
@@ -478,6 +525,39 @@ int main(int argc, char** argv) {
             1 << 20);
     finish(2);
   }
+  if (inject.size() > kMaxInject) {
+    fprintf(stderr, "podworker: --inject-store at most %zu times\n",
+            kMaxInject);
+    finish(2);
+  }
+  for (long long at : inject) {
+    // element 0 already holds 1, and the store must stay inside the buffer
+    if (at < 1 || at >= touch_elems) {
+      fprintf(stderr, "podworker: --inject-store must be in 1..%lld\n",
+              touch_elems - 1);
+      finish(2);
+    }
+    hooks.inject.push_back(static_cast<int>(at));
+  }
+  if (dump_sample_set || hooks.dump_samples) {
+    const std::vector<int> sample =
+        sample_set(static_cast<int>(touch_elems), verify_all);
+    if (hooks.dump_samples && sample.size() > kMaxDumpSamples) {
+      fprintf(stderr, "podworker: --dump-samples takes at most %zu samples\n",
+              kMaxDumpSamples);
+      finish(2);
+    }
+    if (dump_sample_set) {
+      printf("podworker: sample-set m=%zu\n", sample.size());
+      for (size_t j = 0; j < sample.size(); j += 16) {
+        printf("podworker: sample-set");
+        for (size_t k = j; k < j + 16 && k < sample.size(); ++k)
+          printf(" %d", sample[k]);
+        printf("\n");
+      }
+      finish(0);
+    }
+  }
 
   struct sigaction sa{};
   sa.sa_handler = on_term;
@@ -489,7 +569,7 @@ int main(int argc, char** argv) {
   Timing tm;
   if (expect_gpus >= 0) {
     int rc = touch_gpus(expect_gpus, static_cast<int>(touch_elems), verify_all,
-                        &tm);
+                        hooks, &tm);
     if (rc != 0) finish(rc);
   }
 
