@@ -84,6 +84,13 @@ def build_parser() -> argparse.ArgumentParser:
                    metavar="FORMAT:X",
                    help="fail a check whose MX rate for FORMAT (fp8, bf8, "
                         "fp4, fp8xfp4) is below X TFLOP/s; repeatable")
+    p.add_argument("--no-gpu-check-lds", dest="gpu_check_lds",
+                   action="store_false", default=None,
+                   help="skip the per-CU LDS stage")
+    p.add_argument("--gpu-check-lds-require-coverage", action="store_true",
+                   default=None,
+                   help="fail a check that did not reach every compute "
+                        "unit's LDS")
     p.add_argument("--fake-apiserver", action="store_true",
                    help="start an in-process fake Kubernetes apiserver and "
                         "connect to it (self-contained demo; no cluster "
@@ -163,6 +170,10 @@ def main(argv=None) -> int:
     if args.gpu_check_min_mx_tflops is not None:
         cfg.gpu_check_min_mx_tflops = parse_mx_floors(
             args.gpu_check_min_mx_tflops, cfg.gpu_check_min_mx_tflops)
+    if args.gpu_check_lds is not None:
+        cfg.gpu_check_lds = args.gpu_check_lds
+    if args.gpu_check_lds_require_coverage:
+        cfg.gpu_check_lds_require_coverage = True
 
     validate_environment()
     fake_srv = None

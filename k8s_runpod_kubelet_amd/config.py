@@ -119,7 +119,7 @@ class Config:
     evict_on_gpu_failure: bool = True
 
     # Active GPU self-test (gpu/diagnostics.py: HBM pattern, copy bandwidth,
-    # MFMA, block-scaled MX). Off by default; a failed check fences the GPU until an operator
+    # MFMA, block-scaled MX, per-CU LDS). Off by default; a failed check fences the GPU until an operator
     # re-check passes.
     gpu_check_on_start: bool = False       # check idle GPUs before serving
     gpu_check_interval_s: float = 0.0      # periodic re-check; 0 = off
@@ -130,6 +130,9 @@ class Config:
     gpu_check_mx: bool = True              # run the MX (FP8/BF8/FP4) stage
     # MX rate floors in TFLOP/s by format (fp8, bf8, fp4, fp8xfp4); empty = off
     gpu_check_min_mx_tflops: Dict[str, float] = field(default_factory=dict)
+    gpu_check_lds: bool = True             # run the per-CU LDS stage
+    # fail a check that did not reach every compute unit's LDS
+    gpu_check_lds_require_coverage: bool = False
 
     # GPU inventory overrides (mostly for tests / CPU-only dev)
     gpu_count_override: int = -1

@@ -4,9 +4,10 @@ The passive health signal (sysfs/RAS, ``Inventory.refresh_dynamic``) cannot
 see a GPU that still enumerates but no longer stores bits or multiplies
 matrices. ``gpucheck`` (ops/gpucheck/gpucheck.hip) runs real work on an idle
 GPU — an HBM pattern fill/verify, a copy-bandwidth measurement, an exact
-MFMA self-test and an exact self-test of the block-scaled MX (FP8/BF8/FP4)
-matrix path — and this module turns its verdict into the per-GPU
-schedulability gate.
+MFMA self-test, an exact self-test of the block-scaled MX (FP8/BF8/FP4)
+matrix path and a per-CU LDS self-test that names the compute unit of a
+fault — and this module turns its verdict into the per-GPU schedulability
+gate.
 
 The binary always runs as a fresh child process scoped to one GPU, exactly
 like a pod (``device_env``); the kubelet process itself never opens the GPU.
@@ -33,7 +34,8 @@ log = logging.getLogger("gpu.diagnostics")
 
 # gpucheck exit codes (ops/gpucheck/gpucheck.hip)
 EXIT_STAGES = {2: "usage", 11: "hip", 20: "hbm", 21: "mfma", 22: "bandwidth",
-               23: "copy", 24: "mx", 25: "mx_rate"}
+               23: "copy", 24: "mx", 25: "mx_rate", 26: "lds",
+               27: "lds_coverage"}
 MX_FORMATS = ("fp8", "bf8", "fp4", "fp8xfp4")
 RESERVATION_PREFIX = "amdvk-system/gpucheck-"
 
@@ -52,8 +54,8 @@ class GpuCheckResult:
     ok: bool
     exit_code: Optional[int] = None
     # "" on a pass; otherwise the failing stage ("hbm", "copy", "mfma",
-    # "mx", "bandwidth", "mx_rate", "hip", "usage") or "timeout",
-    # "signal N", "bad-output".
+    # "mx", "lds", "bandwidth", "mx_rate", "lds_coverage", "hip", "usage")
+    # or "timeout", "signal N", "bad-output".
     reason: str = ""
     data: Dict[str, Any] = field(default_factory=dict)  # the binary's JSON
     duration_s: float = 0.0
@@ -97,6 +99,18 @@ def first_bad_mx(data: Dict[str, Any]) -> str:
         for name, got in formats.items():
             if isinstance(got, dict) and got.get("bad_waves"):
                 return f"{name} wave {got.get('first_bad_wave')}"
+    return ""
+
+
+def first_bad_lds(data: Dict[str, Any]) -> str:
+    """"xcc2.se1.sh0.cu5 offset 65536 xor 00..01" for the first compute unit
+    with a bad LDS vector in the binary's JSON, or ""."""
+    cus = data.get("lds_bad_cus")
+    if isinstance(cus, list):
+        for cu in cus:
+            if isinstance(cu, dict) and cu.get("bad_vectors"):
+                return (f"{cu.get('where')} offset {cu.get('first_bad_offset')} "
+                        f"xor {cu.get('first_bad_xor')}")
     return ""
 
 
@@ -205,9 +219,15 @@ class DiagnosticsManager:
         floor = float(getattr(self.config, "gpu_check_min_copy_gbs", 0.0) or 0.0)
         args = ["--min-copy-gbs", repr(floor)] if floor > 0 else []
         if not getattr(self.config, "gpu_check_mx", True):
-            return args + ["--mx-waves", "0"]
-        return args + mx_floor_args(
-            getattr(self.config, "gpu_check_min_mx_tflops", None))
+            args += ["--mx-waves", "0"]
+        else:
+            args += mx_floor_args(
+                getattr(self.config, "gpu_check_min_mx_tflops", None))
+        if not getattr(self.config, "gpu_check_lds", True):
+            args += ["--lds-groups", "0"]
+        if getattr(self.config, "gpu_check_lds_require_coverage", False):
+            args += ["--lds-require-coverage"]
+        return args
 
     def check(self, idx: int, operator: bool = False) -> GpuCheckResult:
         """Check one idle GPU. Raises ``UnknownGpuError`` / ``GpuBusyError``.
@@ -280,8 +300,10 @@ class DiagnosticsManager:
         node = {"kind": "Node",
                 "metadata": {"name": self.node_name, "namespace": "default"}}
         where = first_bad_mx(result.data) if result.reason == "mx" else ""
+        lds = first_bad_lds(result.data) if result.reason == "lds" else ""
         message = (f"GPU {idx} failed self-test: stage={result.reason} "
-                   + (f"first_bad_mx={where} " if where else "") +
+                   + (f"first_bad_mx={where} " if where else "")
+                   + (f"lds: {lds} " if lds else "") +
                    f"first_bad_offset={result.data.get('first_bad_offset')} "
                    f"mismatch_vectors={result.data.get('mismatch_vectors')}; "
                    f"GPU fenced until an operator re-check passes")
@@ -385,8 +407,9 @@ def main(argv=None) -> int:
         prog="python -m k8s_runpod_kubelet_amd.gpu.diagnostics",
         description="Run the active GPU self-test on one GPU and print its "
                     "JSON. Exits with the gpucheck exit code (0 pass, 20 HBM, "
-                    "23 copy mismatch, 21 MFMA, 24 MX mismatch, 22 bandwidth, "
-                    "25 MX rate below its floor, 11 HIP error; 1 for a "
+                    "23 copy mismatch, 21 MFMA, 24 MX mismatch, 26 LDS "
+                    "mismatch, 22 bandwidth, 25 MX rate below its floor, "
+                    "27 LDS coverage partial, 11 HIP error; 1 for a "
                     "timeout, signal or unparsable output).")
     p.add_argument("--gpu", type=int, required=True)
     p.add_argument("--bytes", default="1G")
@@ -396,6 +419,10 @@ def main(argv=None) -> int:
                    metavar="FORMAT:X",
                    help="fail if the MX rate of FORMAT (fp8, bf8, fp4, "
                         "fp8xfp4) is below X TFLOP/s; repeatable")
+    p.add_argument("--no-lds", action="store_true",
+                   help="skip the per-CU LDS stage")
+    p.add_argument("--lds-require-coverage", action="store_true",
+                   help="fail (27) unless every compute unit's LDS was tested")
     p.add_argument("--sysfs-root", default="/sys")
     p.add_argument("extra", nargs="*",
                    help="further gpucheck arguments (after --)")
@@ -411,6 +438,10 @@ def main(argv=None) -> int:
         extra += ["--min-copy-gbs", repr(args.min_copy_gbs)]
     for floor in args.min_mx_tflops:
         extra += ["--min-mx-tflops", floor]
+    if args.no_lds:
+        extra += ["--lds-groups", "0"]
+    if args.lds_require_coverage:
+        extra += ["--lds-require-coverage"]
     result = run_gpucheck(args.gpu, inventory, nbytes=parse_size(args.bytes),
                           timeout_s=args.timeout, extra_args=extra)
     print(json.dumps(result.to_dict(), sort_keys=True))

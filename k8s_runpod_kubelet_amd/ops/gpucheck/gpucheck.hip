@@ -1,31 +1,42 @@
 // gpucheck — active GPU self-test run between tenants.
 //
 // Tests visible device 0 (the caller scopes visibility with
-// ROCR_VISIBLE_DEVICES) in four stages:
+// ROCR_VISIBLE_DEVICES) in five stages:
 //   1. HBM fill + verify with a hashed 16-byte pattern and its complement,
 //   2. device-to-device copy bandwidth, with the copied half verified against
 //      the pattern its source holds,
 //   3. an exact-integer MFMA self-test (bf16 32x32x16, no memory loads),
 //   4. an exact self-test of the block-scaled MX path (scaled 32x32x64 MFMA
 //      with e4m3, e5m2 and e2m1 operands and E8M0 scales, in the format pairs
-//      fp8, bf8, fp4 and fp8xfp4) and its measured rate per format pair.
+//      fp8, bf8, fp4 and fp8xfp4) and its measured rate per format pair,
+//   5. an LDS self-test: workgroups that each hold a compute unit's whole
+//      160 KiB LDS fill it with the hashed pattern and its complement and
+//      read it back from another wave; the host counts which compute units
+//      were covered and names the compute unit of a mismatch.
+// Every wave of stages 3 to 5 records where it ran (XCC, shader engine,
+// shader array, compute unit, SIMD), so coverage is reported and a bad wave
+// is located in the hardware.
 // Prints exactly one JSON object as the last stdout line and exits with a
 // stage-specific code (the first that applies, in this order):
 //   0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, 23 copy mismatch,
-//   21 MFMA mismatch, 24 MX mismatch, 22 copy bandwidth below --min-copy-gbs,
-//   25 an MX rate below its --min-mx-tflops.
+//   21 MFMA mismatch, 24 MX mismatch, 26 LDS mismatch, 22 copy bandwidth
+//   below --min-copy-gbs, 25 an MX rate below its --min-mx-tflops, 27 LDS
+//   coverage partial under --lds-require-coverage.
 // `--cpu` runs the HBM stage as host loops over malloc'ed memory and makes no
 // HIP call, so the CLI, JSON and mismatch localisation are testable without
 // a GPU. With an explicit --mfma-waves it also fills the MFMA tiles with a
 // host integer matmul and runs the same comparison over them, and with an
 // explicit --mx-waves it does the same for the MX tiles (rates stay 0 and
-// their floors are ignored).
+// their floors are ignored), and with an explicit --lds-groups it runs the
+// LDS stage's write order, rotated read, injection and judging over a host
+// buffer per group, reporting compute unit `group % 5` for every wave.
 //
 // Flags that exist for the test suite: --dump-pattern, --dump-vectors,
 // --store-variant, --inject-flip, --inject-pass, --inject-copy-flip,
-// --dump-mfma-tile, --inject-mfma, --dump-mx-tile, --inject-mx. The
-// injections flip bits in the region or change the host copy of the MFMA or
-// MX result; they test the checkers.
+// --dump-mfma-tile, --inject-mfma, --dump-mx-tile, --inject-mx, --dump-lds,
+// --dump-lds-where, --inject-lds. The injections flip bits in the region or
+// in the LDS, or change the host copy of the MFMA or MX result; they test
+// the checkers.
 //
 // Build: hipcc --offload-arch=gfx950 -O2 -std=c++17 gpucheck.hip -o gpucheck
 
@@ -40,7 +51,10 @@
 
 #include <algorithm>
 #include <chrono>
+#include <map>
+#include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gpucheck_pattern.h"
@@ -73,8 +87,8 @@ constexpr size_t kCacheResidentBelow = 512ull << 20;
 
 // ---------------------------------------------------------------- kernels
 
-__device__ inline u32x4 pattern_vec(uint64_t seed, uint32_t pass,
-                                    uint64_t index) {
+__host__ __device__ inline u32x4 pattern_vec(uint64_t seed, uint32_t pass,
+                                             uint64_t index) {
   const Vec16 v = gpucheck::pattern(seed, pass, index);
   u32x4 x;
   x.x = static_cast<unsigned int>(v.lo);
@@ -82,6 +96,64 @@ __device__ inline u32x4 pattern_vec(uint64_t seed, uint32_t pass,
   x.z = static_cast<unsigned int>(v.hi);
   x.w = static_cast<unsigned int>(v.hi >> 32);
   return x;
+}
+
+// Where a wave runs, from two scalar register reads. The fields of HW_ID are
+// the GFX9 layout; a CU key packs the XCC id with the shader engine, shader
+// array and compute unit and leaves out everything that differs between the
+// waves of one compute unit (wave, SIMD, pipe, queue).
+//
+// Measured on an MI355X (256 compute units) with 512 workgroups of
+// lds_selftest, three runs alike: the four waves of every workgroup report
+// one CU key and the SIMD ids {0, 1, 2, 3}; the keys are exactly 256,
+// 32 per XCC id 0..7 and 64 per se_id 0..3 (bit 15 is always 0), sh_id is
+// always 0, and cu_id runs 0..8 with 19 to 32 compute units per value (the
+// harvested ones differ between shader engines). So this table is right for
+// gfx950: no mask below lets a per-wave bit in or drops a bit that tells two
+// compute units apart.
+struct HwField {
+  int shift, bits;
+};
+constexpr int kHwRegHwId = 4;
+constexpr int kHwRegXccId = 20;
+constexpr HwField kHwSimd{4, 2};
+constexpr HwField kHwCu{8, 4};
+constexpr HwField kHwSh{12, 1};
+constexpr HwField kHwSe{13, 3};
+constexpr HwField kXccId{0, 4};
+// CU key: cu [3:0], sh [4], se [7:5], xcc [11:8].
+constexpr int kKeyShShift = 4, kKeySeShift = 5, kKeyXccShift = 8;
+
+// The immediate of s_getreg_b32: register id, first bit, field width - 1.
+constexpr int hwreg(int id, int offset, int bits) {
+  return id | (offset << 6) | ((bits - 1) << 11);
+}
+
+constexpr uint32_t hw_field(uint32_t reg, HwField f) {
+  return (reg >> f.shift) & ((1u << f.bits) - 1);
+}
+
+struct WaveWhere {
+  uint32_t cu_key, simd;
+};
+
+__device__ inline WaveWhere wave_where() {
+  const uint32_t hw = __builtin_amdgcn_s_getreg(hwreg(kHwRegHwId, 0, 32));
+  const uint32_t xcc = __builtin_amdgcn_s_getreg(
+      hwreg(kHwRegXccId, kXccId.shift, kXccId.bits));
+  WaveWhere w;
+  w.cu_key = hw_field(hw, kHwCu) | (hw_field(hw, kHwSh) << kKeyShShift) |
+             (hw_field(hw, kHwSe) << kKeySeShift) | (xcc << kKeyXccShift);
+  w.simd = hw_field(hw, kHwSimd);
+  return w;
+}
+
+// where[2 * wave] = CU key, where[2 * wave + 1] = SIMD id: two ordinary
+// vector stores from the calling lane (one lane per wave calls this).
+__device__ inline void store_where(uint32_t* __restrict__ where, size_t wave) {
+  const WaveWhere w = wave_where();
+  where[2 * wave] = w.cu_key;
+  where[2 * wave + 1] = w.simd;
 }
 
 // One 16-byte vector per lane per trip; consecutive lanes write consecutive
@@ -145,9 +217,10 @@ __global__ __launch_bounds__(kBlock) void vec_copy(u32x4* __restrict__ dst,
 // generated in registers, then stores it to out[wave][row][col]. Lane l
 // (r = l & 31, h = l >> 5) holds A[r][8h+j] and B[8h+j][r] of each 16-wide
 // k-step in element j; accumulator register g is D[(g&3)+8(g>>2)+4h][r].
-__global__ __launch_bounds__(kBlock) void mfma_selftest(float* __restrict__ out,
-                                                        uint32_t nwaves,
-                                                        uint64_t seed) {
+// Lane 0 also stores where the wave ran to where[wave].
+__global__ __launch_bounds__(kBlock) void mfma_selftest(
+    float* __restrict__ out, uint32_t* __restrict__ where, uint32_t nwaves,
+    uint64_t seed) {
   const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   // Wave-uniform: surplus waves of the last workgroup leave whole, so every
   // MFMA below runs with a full EXEC mask.
@@ -180,6 +253,7 @@ __global__ __launch_bounds__(kBlock) void mfma_selftest(float* __restrict__ out,
     const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
     tile[row * 32 + r] = acc[g];
   }
+  if (lane == 0) store_where(where, wave);
 }
 
 // One lane's 32 elements of an MX operand for one 64-wide k-step, packed
@@ -246,9 +320,9 @@ __device__ inline f32x16 mx_step(f32x16 acc, uint64_t key_a, uint64_t key_b,
 // of both lanes r and r + 32.
 // The C/D map depends on the shape only, so it is mfma_selftest's.
 template <int kFmt>
-__global__ __launch_bounds__(kBlock) void mx_selftest(float* __restrict__ out,
-                                                      uint32_t nwaves,
-                                                      uint64_t seed) {
+__global__ __launch_bounds__(kBlock) void mx_selftest(
+    float* __restrict__ out, uint32_t* __restrict__ where, uint32_t nwaves,
+    uint64_t seed) {
   const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   // Wave-uniform, as in mfma_selftest: EXEC is full at every MFMA.
   if (wave >= nwaves) return;
@@ -276,6 +350,7 @@ __global__ __launch_bounds__(kBlock) void mx_selftest(float* __restrict__ out,
     const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
     tile[row * 32 + r] = acc[g];
   }
+  if (lane == 0) store_where(where, wave);
 }
 
 // Timed: every wave issues 4 * trips scaled MFMAs of one format over four
@@ -314,6 +389,135 @@ __global__ __launch_bounds__(kBlock) void mx_rate(float* __restrict__ sink,
   float sum = 0.0f;
   for (int g = 0; g < 16; ++g) sum += acc0[g] + acc1[g] + acc2[g] + acc3[g];
   sink[tid] = sum;
+}
+
+// The LDS self-test. One record per workgroup, updated only by waves that
+// saw a mismatch.
+struct LdsRecord {
+  unsigned long long bad;    // mismatching vectors
+  unsigned long long first;  // min of lds_pack(round, pass, vector); kNoBad
+  u32x4 first_xor;           // got ^ want of that vector
+};
+
+constexpr int kMaxLdsInject = 4;
+struct LdsInjections {
+  uint32_t n;
+  struct {
+    uint32_t group, round, pass, dword, mask;
+  } at[kMaxLdsInject];
+};
+
+__host__ __device__ inline unsigned long long lds_pack(uint32_t round,
+                                                       uint32_t pass,
+                                                       uint32_t vector) {
+  return (static_cast<unsigned long long>(round) << 15) | (pass << 14) | vector;
+}
+
+// One 256-thread workgroup owns all 160 KiB of its compute unit's LDS (so no
+// second workgroup of this kernel shares the compute unit) and, `rounds`
+// times, for the pattern and then its complement: thread t writes vectors
+// t + 256 j (consecutive lanes, consecutive ds_write_b128), thread 0 applies
+// a matching injection, and thread t reads back and compares vectors
+// ((t + 64) & 255) + 256 j, those the next wave wrote. Every LDS index is
+// below 256 * 40 = kLdsVectors by construction; an injection's dword is
+// checked against the array besides.
+//
+// The whole LDS is the array under test, so the reduction uses none of it:
+// shuffles within a wave, then one integer atomic pair per wave that saw a
+// mismatch; after a barrier the lane whose own first mismatch is the
+// workgroup's minimum stores that vector's XOR. Each vector is read by one
+// lane, so exactly one lane matches. Lane 0 of each wave stores where the
+// wave ran to where[4 * group + wave]; the four must share one CU key.
+// `dump`, when not null, receives what the chosen workgroup read back in the
+// chosen round and pass (kLdsVectors vectors) and after them, per vector,
+// the thread that read it (kLdsVectors dwords): the only trace of which
+// wave did the reading.
+//
+// The HW_ID fields as measured on an MI355X are at wave_where. There 512
+// workgroups (two per compute unit) reached all 256 compute units in one
+// launch, every time: the first 256 workgroups already sat on 256 different
+// compute units.
+__global__ __launch_bounds__(kBlock) void lds_selftest(
+    LdsRecord* __restrict__ records, uint32_t* __restrict__ where,
+    uint64_t seed, uint32_t round_base, uint32_t rounds, LdsInjections inj,
+    u32x4* __restrict__ dump, uint32_t dump_group, uint32_t dump_round,
+    uint32_t dump_pass) {
+  __shared__ u32x4 lds[gpucheck::kLdsVectors];
+  constexpr int trips = gpucheck::kLdsVectors / kBlock;
+  const uint32_t t = threadIdx.x;
+  const uint32_t reader = (t + 64) & (kBlock - 1);
+  const uint32_t group = blockIdx.x;
+  unsigned long long bad = 0;
+  unsigned long long first = kNoBad;
+  u32x4 first_xor = {0, 0, 0, 0};
+  for (uint32_t r = 0; r < rounds; ++r) {
+    const uint32_t round = round_base + r;
+    const uint64_t key = gpucheck::lds_key(seed, group, round);
+    for (uint32_t pass = 0; pass < 2; ++pass) {
+      for (int j = 0; j < trips; ++j) {
+        const uint32_t i = t + kBlock * j;
+        lds[i] = pattern_vec(key, pass, i);
+      }
+      __syncthreads();
+      // Uniform over the workgroup: every thread takes the barrier or none.
+      bool hit = false;
+      for (uint32_t k = 0; k < inj.n && k < kMaxLdsInject; ++k)
+        hit = hit || (inj.at[k].group == group && inj.at[k].round == round &&
+                      inj.at[k].pass == pass);
+      if (hit) {
+        if (t == 0)
+          for (uint32_t k = 0; k < inj.n && k < kMaxLdsInject; ++k)
+            if (inj.at[k].group == group && inj.at[k].round == round &&
+                inj.at[k].pass == pass &&
+                inj.at[k].dword < 4u * gpucheck::kLdsVectors)
+              lds[inj.at[k].dword >> 2][inj.at[k].dword & 3] ^= inj.at[k].mask;
+        __syncthreads();
+      }
+      const bool dumping = dump != nullptr && group == dump_group &&
+                           round == dump_round && pass == dump_pass;
+      for (int j = 0; j < trips; ++j) {
+        const uint32_t i = reader + kBlock * j;
+        const u32x4 got = lds[i];
+        const u32x4 want = pattern_vec(key, pass, i);
+        if (got.x != want.x || got.y != want.y || got.z != want.z ||
+            got.w != want.w) {
+          ++bad;
+          const unsigned long long packed = lds_pack(round, pass, i);
+          if (packed < first) {
+            first = packed;
+            first_xor = got ^ want;
+          }
+        }
+        if (dumping) {
+          dump[i] = got;
+          reinterpret_cast<uint32_t*>(dump + gpucheck::kLdsVectors)[i] = t;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  unsigned long long wave_bad = bad;
+  unsigned long long wave_first = first;
+  for (int off = 32; off > 0; off >>= 1) {
+    wave_bad += __shfl_xor(wave_bad, off);
+    const unsigned long long other = __shfl_xor(wave_first, off);
+    wave_first = other < wave_first ? other : wave_first;
+  }
+  LdsRecord* rec = &records[group];
+  if (wave_bad != 0) {  // wave-uniform
+    if ((t & 63) == 0) {
+      atomicAdd(&rec->bad, wave_bad);
+      atomicMin(&rec->first, wave_first);
+    }
+    // The atomics have reached memory before this wave passes the barrier.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  }
+  __syncthreads();
+  if (first != kNoBad &&
+      __hip_atomic_load(&rec->first, __ATOMIC_RELAXED,
+                        __HIP_MEMORY_SCOPE_AGENT) == first)
+    rec->first_xor = first_xor;
+  if ((t & 63) == 0) store_where(where, 4 * static_cast<size_t>(group) + (t >> 6));
 }
 
 // ---------------------------------------------------------------- options
@@ -355,6 +559,18 @@ struct Options {
   std::vector<MxInject> mx_inject;
   double min_mx_tflops[gpucheck::kMxFormats] = {0, 0, 0, 0};
   uint64_t mx_rate_instr = 65536;  // timed MFMAs per wave and launch
+  // LDS stage.
+  long lds_groups = -1;  // -1: 2 x multiProcessorCount (0 under --cpu)
+  uint32_t lds_rounds = 4;
+  uint32_t lds_max_launches = 8;
+  bool lds_require_coverage = false;
+  bool dump_lds = false;
+  uint32_t dump_lds_group = 0, dump_lds_round = 0, dump_lds_pass = 0;
+  bool dump_lds_where = false;
+  struct LdsInject {
+    uint32_t group, round, pass, byte, bit;
+  };
+  std::vector<LdsInject> lds_inject;
 };
 
 constexpr size_t kMaxFlips = 16;
@@ -409,6 +625,9 @@ int usage(const char* why, const char* arg) {
           "[--mx-rate-instr N]\n"
           "                (FORMAT: fp8, bf8, fp4 or fp8xfp4; --mx-waves 0 "
           "skips the MX stage)\n"
+          "                [--lds-groups N] [--lds-rounds R] "
+          "[--lds-max-launches L] [--lds-require-coverage]\n"
+          "                (--lds-groups 0 skips the LDS stage)\n"
           "       checks of the checkers:\n"
           "                [--dump-pattern] [--dump-vectors I[,J,...]] "
           "[--dump-mfma-tile W]\n"
@@ -416,11 +635,15 @@ int usage(const char* why, const char* arg) {
           "[--inject-copy-flip OFFSET:BIT]\n"
           "                [--inject-mfma WAVE:ELEM]... "
           "[--dump-mx-tile FORMAT:WAVE]\n"
-          "                [--inject-mx FORMAT:WAVE:ELEM]...\n"
+          "                [--inject-mx FORMAT:WAVE:ELEM]... "
+          "[--dump-lds GROUP:ROUND:PASS] [--dump-lds-where]\n"
+          "                [--inject-lds GROUP:ROUND:PASS:BYTE:BIT]...\n"
           "exit: 0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, "
           "23 copy mismatch, 21 MFMA mismatch,\n"
-          "      24 MX mismatch, 22 copy bandwidth below --min-copy-gbs, "
-          "25 MX rate below --min-mx-tflops\n",
+          "      24 MX mismatch, 26 LDS mismatch, 22 copy bandwidth below "
+          "--min-copy-gbs,\n"
+          "      25 MX rate below --min-mx-tflops, 27 LDS coverage partial "
+          "under --lds-require-coverage\n",
           why, arg ? " " : "", arg ? arg : "");
   return 2;
 }
@@ -431,6 +654,19 @@ bool parse_pair(const char* v, uint64_t* a, uint64_t* b) {
   return colon != nullptr &&
          parse_u64(std::string(v, colon - v).c_str(), a, false) &&
          parse_u64(colon + 1, b, false);
+}
+
+// "A:B:...": exactly `n` unsigned integers.
+bool parse_fields(const char* v, size_t n, uint64_t* out) {
+  if (v == nullptr) return false;
+  std::string rest = v;
+  for (size_t k = 0; k < n; ++k) {
+    const size_t colon = rest.find(':');
+    if ((colon == std::string::npos) != (k + 1 == n)) return false;
+    if (!parse_u64(rest.substr(0, colon).c_str(), &out[k], false)) return false;
+    if (k + 1 < n) rest = rest.substr(colon + 1);
+  }
+  return true;
 }
 
 // "FORMAT:REST": the index of the named MX format, or -1; *rest is REST.
@@ -556,6 +792,44 @@ int parse_args(int argc, char** argv, Options* o) {
       if (!parse_u64(next(), &u, false) || u == 0 || u > (1ull << 30))
         return usage("bad value for", "--mx-rate-instr");
       o->mx_rate_instr = u;
+    } else if (a == "--lds-groups") {
+      if (!parse_u64(next(), &u, false) || u > 65536)
+        return usage("bad value for", "--lds-groups");
+      o->lds_groups = static_cast<long>(u);
+    } else if (a == "--lds-rounds") {
+      if (!parse_u64(next(), &u, false) || u == 0 || u > 1024)
+        return usage("bad value for", "--lds-rounds");
+      o->lds_rounds = static_cast<uint32_t>(u);
+    } else if (a == "--lds-max-launches") {
+      if (!parse_u64(next(), &u, false) || u == 0 || u > 64)
+        return usage("bad value for", "--lds-max-launches");
+      o->lds_max_launches = static_cast<uint32_t>(u);
+    } else if (a == "--lds-require-coverage") {
+      o->lds_require_coverage = true;
+    } else if (a == "--dump-lds-where") {
+      o->dump_lds_where = true;
+    } else if (a == "--dump-lds") {
+      uint64_t f[3];
+      if (!parse_fields(next(), 3, f) || f[0] >= 65536 || f[1] >= 1024 ||
+          f[2] > 1)
+        return usage("bad value for", "--dump-lds");
+      o->dump_lds = true;
+      o->dump_lds_group = static_cast<uint32_t>(f[0]);
+      o->dump_lds_round = static_cast<uint32_t>(f[1]);
+      o->dump_lds_pass = static_cast<uint32_t>(f[2]);
+    } else if (a == "--inject-lds") {
+      uint64_t f[5];
+      if (!parse_fields(next(), 5, f) || f[0] >= 65536 || f[1] >= 1024 ||
+          f[2] > 1 || f[3] >= static_cast<uint64_t>(gpucheck::kLdsBytes) ||
+          f[4] > 7)
+        return usage("bad value for", "--inject-lds");
+      if (o->lds_inject.size() == kMaxLdsInject)
+        return usage("too many", "--inject-lds");
+      o->lds_inject.push_back({static_cast<uint32_t>(f[0]),
+                               static_cast<uint32_t>(f[1]),
+                               static_cast<uint32_t>(f[2]),
+                               static_cast<uint32_t>(f[3]),
+                               static_cast<uint32_t>(f[4])});
     } else {
       return usage("unknown argument", a.c_str());
     }
@@ -598,6 +872,16 @@ int check_mx_args(const Options& o, long nwaves) {
   for (const Options::MxInject& m : o.mx_inject)
     if (m.wave >= nwaves)
       return usage("--inject-mx wave is outside the run", nullptr);
+  return 0;
+}
+
+// The same for the LDS flags: they name workgroups and rounds of the run.
+int check_lds_args(const Options& o, long groups) {
+  if (o.dump_lds && (o.dump_lds_group >= groups || o.dump_lds_round >= o.lds_rounds))
+    return usage("--dump-lds group or round is outside the run", nullptr);
+  for (const Options::LdsInject& m : o.lds_inject)
+    if (m.group >= groups || m.round >= o.lds_rounds)
+      return usage("--inject-lds group or round is outside the run", nullptr);
   return 0;
 }
 
@@ -646,7 +930,36 @@ struct Report {
   MxFormatResult mx_formats[gpucheck::kMxFormats];
   bool mx_tile_valid = false;
   std::vector<long> mx_tile;  // values times 16
+  // Where the MFMA and MX waves ran: [cu key, simd] per wave (MX: per format
+  // and wave). Empty under --cpu.
+  std::vector<uint32_t> mfma_where, mx_where;
+  // LDS
+  const char* lds = "skipped";
+  std::string lds_skip_reason;
+  long lds_groups = 0, lds_launches = 0, lds_bad_groups = 0;
+  std::set<uint32_t> lds_cus;  // CU keys seen
+  struct LdsBadCu {
+    uint64_t bad_vectors = 0;
+    unsigned long long first = kNoBad;  // lds_pack(round, pass, vector)
+    Vec16 first_xor{0, 0};
+  };
+  std::map<uint32_t, LdsBadCu> lds_bad_cus;  // by CU key
+  double lds_gbs = 0;
+  std::vector<uint32_t> lds_where;  // first launch: [cu key, simd] per wave
+  bool lds_dump_valid = false;
+  uint64_t lds_dump_fnv64 = 0;
+  long lds_dump_same_wave_reads = 0;
+  std::vector<std::string> lds_dump_vectors;
 };
+
+std::string where_name(uint32_t key) {
+  char buf[64];
+  snprintf(buf, sizeof(buf), "xcc%u.se%u.sh%u.cu%u", key >> kKeyXccShift,
+           (key >> kKeySeShift) & ((1u << kHwSe.bits) - 1),
+           (key >> kKeyShShift) & ((1u << kHwSh.bits) - 1),
+           key & ((1u << kHwCu.bits) - 1));
+  return buf;
+}
 
 std::string hex128(const Vec16& v) {
   char buf[40];
@@ -982,19 +1295,58 @@ void run_mfma_cpu(const Options& o, long nwaves, Report* rep) {
   judge_mfma(host, nwaves, o, rep);
 }
 
+// [cu key, simd] per wave on the device, preset to all ones.
+struct WhereBuffer {
+  uint32_t* dev = nullptr;
+  size_t nwaves;
+  explicit WhereBuffer(size_t n) : nwaves(n) {
+    HIP_CHECK(hipMalloc(&dev, 2 * n * sizeof(uint32_t)));
+    HIP_CHECK(hipMemset(dev, 0xFF, 2 * n * sizeof(uint32_t)));
+  }
+  ~WhereBuffer() {
+    if (dev) (void)hipFree(dev);
+  }
+  std::vector<uint32_t> fetch() {
+    std::vector<uint32_t> host(2 * nwaves);
+    HIP_CHECK(hipMemcpy(host.data(), dev, host.size() * sizeof(uint32_t),
+                        hipMemcpyDeviceToHost));
+    return host;
+  }
+};
+
+// Distinct CU keys and distinct (CU key, SIMD) pairs of a where list.
+void count_where(const std::vector<uint32_t>& where, size_t* cus, size_t* simds) {
+  std::set<uint32_t> keys;
+  std::set<std::pair<uint32_t, uint32_t>> pairs;
+  for (size_t w = 0; 2 * w + 1 < where.size(); ++w) {
+    keys.insert(where[2 * w]);
+    pairs.insert({where[2 * w], where[2 * w + 1]});
+  }
+  *cus = keys.size();
+  *simds = pairs.size();
+}
+
+// "xcc2.se1.sh0.cu5" of wave `w` of a where list, "" without one.
+std::string where_of(const std::vector<uint32_t>& where, long w) {
+  if (w < 0 || 2 * static_cast<size_t>(w) + 1 >= where.size()) return "";
+  return where_name(where[2 * w]);
+}
+
 void run_mfma(const Options& o, long nwaves, Report* rep) {
   const size_t nfloat = static_cast<size_t>(nwaves) * 32 * 32;
   float* dev = nullptr;
   HIP_CHECK(hipMalloc(&dev, nfloat * sizeof(float)));
   HIP_CHECK(hipMemset(dev, 0xFF, nfloat * sizeof(float)));
+  WhereBuffer where(static_cast<size_t>(nwaves));
   const unsigned int blocks = static_cast<unsigned int>((nwaves + 3) / 4);
   hipLaunchKernelGGL(mfma_selftest, dim3(blocks), dim3(kBlock), 0, 0, dev,
-                     static_cast<uint32_t>(nwaves), o.seed);
+                     where.dev, static_cast<uint32_t>(nwaves), o.seed);
   HIP_CHECK(hipGetLastError());
   std::vector<float> host(nfloat);
   HIP_CHECK(hipMemcpy(host.data(), dev, nfloat * sizeof(float),
                       hipMemcpyDeviceToHost));
   HIP_CHECK(hipFree(dev));
+  rep->mfma_where = where.fetch();
   judge_mfma(host, nwaves, o, rep);
 }
 
@@ -1163,13 +1515,14 @@ void run_mx_cpu(const Options& o, long nwaves, Report* rep) {
 }
 
 template <int kFmt>
-void launch_mx_formats(float* dev, long nwaves, uint64_t seed) {
+void launch_mx_formats(float* dev, uint32_t* where, long nwaves, uint64_t seed) {
   const unsigned int blocks = static_cast<unsigned int>((nwaves + 3) / 4);
   hipLaunchKernelGGL(mx_selftest<kFmt>, dim3(blocks), dim3(kBlock), 0, 0,
                      dev + static_cast<size_t>(kFmt) * nwaves * 32 * 32,
+                     where + static_cast<size_t>(kFmt) * nwaves * 2,
                      static_cast<uint32_t>(nwaves), seed);
   if constexpr (kFmt + 1 < gpucheck::kMxFormats)
-    launch_mx_formats<kFmt + 1>(dev, nwaves, seed);
+    launch_mx_formats<kFmt + 1>(dev, where, nwaves, seed);
 }
 
 // Median of five timed launches after one warm-up, as the copy stage; two
@@ -1200,12 +1553,15 @@ void run_mx(const Options& o, long nwaves, int compute_units, Report* rep) {
   float* dev = nullptr;
   HIP_CHECK(hipMalloc(&dev, nfloat * sizeof(float)));
   HIP_CHECK(hipMemset(dev, 0xFF, nfloat * sizeof(float)));
-  launch_mx_formats<0>(dev, nwaves, o.seed);
+  // Format-major like the tiles: where[2 * (f * nwaves + w)].
+  WhereBuffer where(static_cast<size_t>(gpucheck::kMxFormats) * nwaves);
+  launch_mx_formats<0>(dev, where.dev, nwaves, o.seed);
   HIP_CHECK(hipGetLastError());
   std::vector<float> host(nfloat);
   HIP_CHECK(hipMemcpy(host.data(), dev, nfloat * sizeof(float),
                       hipMemcpyDeviceToHost));
   HIP_CHECK(hipFree(dev));
+  rep->mx_where = where.fetch();
   judge_mx(host, nwaves, o, rep);
 
   const unsigned int blocks =
@@ -1221,6 +1577,198 @@ void run_mx(const Options& o, long nwaves, int compute_units, Report* rep) {
     if (o.min_mx_tflops[f] > 0 &&
         rep->mx_formats[f].tflops < o.min_mx_tflops[f])
       rep->mx_rate = "fail";
+}
+
+// -------------------------------------------------------------- LDS stage
+
+uint64_t fnv1a64(const unsigned char* p, size_t n) {
+  uint64_t h = 0xCBF29CE484222325ull;
+  for (size_t i = 0; i < n; ++i) h = (h ^ p[i]) * 0x100000001B3ull;
+  return h;
+}
+
+constexpr int kLdsDumpVectors[] = {0, 1, 255, 256, 4095, 4096, 4097, 10238, 10239};
+
+constexpr size_t kLdsDumpBytes =
+    gpucheck::kLdsBytes + gpucheck::kLdsVectors * sizeof(uint32_t);
+
+// `bytes`: the kLdsBytes one workgroup read back in the dumped round and
+// pass; `readers`: the thread that read each vector. Thread i % 256 wrote
+// vector i, so a vector whose reader is in that thread's wave was not read
+// back across waves.
+void record_lds_dump(const unsigned char* bytes, const uint32_t* readers,
+                     Report* rep) {
+  rep->lds_dump_valid = true;
+  rep->lds_dump_same_wave_reads = 0;
+  for (uint32_t i = 0; i < static_cast<uint32_t>(gpucheck::kLdsVectors); ++i)
+    if (readers[i] >= kBlock || (readers[i] >> 6) == ((i % kBlock) >> 6))
+      ++rep->lds_dump_same_wave_reads;
+  rep->lds_dump_fnv64 = fnv1a64(bytes, gpucheck::kLdsBytes);
+  for (int i : kLdsDumpVectors) {
+    Vec16 v;
+    memcpy(&v, bytes + 16 * static_cast<size_t>(i), 16);
+    rep->lds_dump_vectors.push_back(hex128(v));
+  }
+}
+
+LdsInjections lds_injections(const Options& o) {
+  LdsInjections inj = {};
+  for (const Options::LdsInject& m : o.lds_inject) {
+    auto& at = inj.at[inj.n++];
+    at.group = m.group;
+    at.round = m.round;
+    at.pass = m.pass;
+    at.dword = m.byte / 4;
+    at.mask = 1u << (8 * (m.byte % 4) + m.bit);
+  }
+  return inj;
+}
+
+// One launch's records and where list (four waves per group) into the
+// report: the CU keys seen, and the mismatches merged by compute unit.
+void judge_lds(const std::vector<LdsRecord>& records,
+               const std::vector<uint32_t>& where, Report* rep) {
+  for (size_t g = 0; g < records.size(); ++g) {
+    for (int w = 0; w < 4; ++w) rep->lds_cus.insert(where[2 * (4 * g + w)]);
+    const LdsRecord& rec = records[g];
+    if (rec.bad == 0) continue;
+    ++rep->lds_bad_groups;
+    Report::LdsBadCu& cu = rep->lds_bad_cus[where[2 * (4 * g)]];
+    cu.bad_vectors += rec.bad;
+    if (rec.first < cu.first) {
+      cu.first = rec.first;
+      cu.first_xor.lo = rec.first_xor.x | (static_cast<uint64_t>(rec.first_xor.y) << 32);
+      cu.first_xor.hi = rec.first_xor.z | (static_cast<uint64_t>(rec.first_xor.w) << 32);
+    }
+  }
+  rep->lds = rep->lds_bad_groups ? "fail" : "pass";
+}
+
+// --cpu: what lds_selftest does, in its order, over a host buffer per group:
+// this exercises the injection, the record, judge_lds and the JSON, not a
+// device. Every wave of group g reports compute unit g % 5 and its own
+// number as the SIMD.
+void run_lds_cpu(const Options& o, long groups, Report* rep) {
+  constexpr int trips = gpucheck::kLdsVectors / kBlock;
+  rep->lds_groups = groups;
+  rep->lds_launches = 1;
+  const LdsInjections inj = lds_injections(o);
+  std::vector<LdsRecord> records(static_cast<size_t>(groups));
+  std::vector<uint32_t> where(static_cast<size_t>(groups) * 8);
+  std::vector<u32x4> lds(gpucheck::kLdsVectors), dump(gpucheck::kLdsVectors);
+  std::vector<uint32_t> readers(gpucheck::kLdsVectors);
+  for (long g = 0; g < groups; ++g) {
+    const uint32_t group = static_cast<uint32_t>(g);
+    LdsRecord rec = {0, kNoBad, {0, 0, 0, 0}};
+    for (uint32_t round = 0; round < o.lds_rounds; ++round) {
+      const uint64_t key = gpucheck::lds_key(o.seed, group, round);
+      for (uint32_t pass = 0; pass < 2; ++pass) {
+        for (uint32_t t = 0; t < kBlock; ++t)
+          for (int j = 0; j < trips; ++j)
+            lds[t + kBlock * j] = pattern_vec(key, pass, t + kBlock * j);
+        for (uint32_t k = 0; k < inj.n; ++k)
+          if (inj.at[k].group == group && inj.at[k].round == round &&
+              inj.at[k].pass == pass)
+            lds[inj.at[k].dword >> 2][inj.at[k].dword & 3] ^= inj.at[k].mask;
+        const bool dumping = o.dump_lds && group == o.dump_lds_group &&
+                             round == o.dump_lds_round && pass == o.dump_lds_pass;
+        for (uint32_t t = 0; t < kBlock; ++t)
+          for (int j = 0; j < trips; ++j) {
+            const uint32_t i = ((t + 64) & (kBlock - 1)) + kBlock * j;
+            const u32x4 got = lds[i];
+            const u32x4 want = pattern_vec(key, pass, i);
+            if (got.x != want.x || got.y != want.y || got.z != want.z ||
+                got.w != want.w) {
+              ++rec.bad;
+              const unsigned long long packed = lds_pack(round, pass, i);
+              if (packed < rec.first) {
+                rec.first = packed;
+                rec.first_xor = got ^ want;
+              }
+            }
+            if (dumping) {
+              dump[i] = got;
+              readers[i] = t;
+            }
+          }
+        if (dumping)
+          record_lds_dump(reinterpret_cast<const unsigned char*>(dump.data()),
+                          readers.data(), rep);
+      }
+    }
+    records[g] = rec;
+    for (uint32_t w = 0; w < 4; ++w) {
+      where[2 * (4 * g + w)] = group % 5;
+      where[2 * (4 * g + w) + 1] = w;
+    }
+  }
+  rep->lds_where = where;
+  judge_lds(records, where, rep);
+}
+
+// Launches `groups` workgroups, again with fresh rounds while compute units
+// remain unseen and launches remain: a workgroup holds a whole LDS, so two
+// never share a compute unit, and which compute units the dispatcher picked
+// is known only from the CU keys that come back.
+void run_lds(const Options& o, long groups, const hipDeviceProp_t& prop,
+             Report* rep) {
+  rep->lds_groups = groups;
+  hipFuncAttributes attr;
+  HIP_CHECK(hipFuncGetAttributes(&attr,
+                                 reinterpret_cast<const void*>(lds_selftest)));
+  if (prop.sharedMemPerBlock < static_cast<size_t>(gpucheck::kLdsBytes) ||
+      attr.sharedSizeBytes != static_cast<size_t>(gpucheck::kLdsBytes)) {
+    rep->lds_skip_reason =
+        "needs 163840 bytes of LDS per workgroup: the device offers " +
+        std::to_string(prop.sharedMemPerBlock) + ", the kernel uses " +
+        std::to_string(attr.sharedSizeBytes);
+    return;
+  }
+  const size_t n = static_cast<size_t>(groups);
+  LdsRecord* records = nullptr;
+  u32x4* dump = nullptr;
+  HIP_CHECK(hipMalloc(&records, n * sizeof(LdsRecord)));
+  if (o.dump_lds) {
+    HIP_CHECK(hipMalloc(&dump, kLdsDumpBytes));
+    HIP_CHECK(hipMemset(dump, 0xFF, kLdsDumpBytes));
+  }
+  WhereBuffer where(4 * n);
+  GpuTimer timer;
+  timer.init();
+  const LdsInjections inj = lds_injections(o);
+  const std::vector<LdsRecord> clean(n, LdsRecord{0, kNoBad, {0, 0, 0, 0}});
+  std::vector<LdsRecord> host(n);
+  double seconds = 0;
+  for (uint32_t launch = 0; launch < o.lds_max_launches; ++launch) {
+    HIP_CHECK(hipMemcpy(records, clean.data(), n * sizeof(LdsRecord),
+                        hipMemcpyHostToDevice));
+    timer.begin();
+    // Injections and the dump name rounds of the first launch.
+    hipLaunchKernelGGL(lds_selftest, dim3(static_cast<unsigned int>(n)),
+                       dim3(kBlock), 0, 0, records, where.dev, o.seed,
+                       launch * o.lds_rounds, o.lds_rounds, inj,
+                       launch == 0 ? dump : nullptr, o.dump_lds_group,
+                       o.dump_lds_round, o.dump_lds_pass);
+    seconds = timer.end();
+    HIP_CHECK(hipMemcpy(host.data(), records, n * sizeof(LdsRecord),
+                        hipMemcpyDeviceToHost));
+    const std::vector<uint32_t> ran = where.fetch();
+    if (launch == 0) rep->lds_where = ran;
+    ++rep->lds_launches;
+    judge_lds(host, ran, rep);
+    if (rep->lds_cus.size() >= static_cast<size_t>(prop.multiProcessorCount))
+      break;
+  }
+  rep->lds_gbs = gbs(2.0 * 2.0 * gpucheck::kLdsBytes * o.lds_rounds *
+                         static_cast<double>(n), seconds);
+  if (o.dump_lds) {
+    std::vector<uint32_t> words(kLdsDumpBytes / sizeof(uint32_t));
+    HIP_CHECK(hipMemcpy(words.data(), dump, kLdsDumpBytes, hipMemcpyDeviceToHost));
+    record_lds_dump(reinterpret_cast<const unsigned char*>(words.data()),
+                    words.data() + gpucheck::kLdsBytes / sizeof(uint32_t), rep);
+    HIP_CHECK(hipFree(dump));
+  }
+  HIP_CHECK(hipFree(records));
 }
 
 // ------------------------------------------------------------------- JSON
@@ -1240,8 +1788,41 @@ std::string json_escape(const std::string& s) {
   return out;
 }
 
+constexpr size_t kMaxLdsBadCus = 8;
+
+// Every compute unit's LDS was visited. Under --cpu there are no compute
+// units, so a stage that ran is complete.
+bool lds_coverage_full(const Report& r) {
+  return strcmp(r.lds, "skipped") != 0 &&
+         r.lds_cus.size() >= static_cast<size_t>(r.compute_units);
+}
+
+// Exit 27: an untested compute unit is a failure only on request, and never
+// under --cpu, which has no compute units.
+bool lds_coverage_required_and_partial(const Options& o, const Report& r) {
+  return o.lds_require_coverage && !o.cpu && !lds_coverage_full(r);
+}
+
+// "name":[[[key,simd] x per_group] per group], (flat pairs when per_group
+// is 1)
+void print_where_list(const char* name, const std::vector<uint32_t>& where,
+                      size_t per_group) {
+  printf("\"%s\":[", name);
+  const size_t waves = where.size() / 2;
+  for (size_t w = 0; w < waves; ++w) {
+    if (per_group > 1 && w % per_group == 0) printf("%s[", w ? "," : "");
+    printf("%s[%u,%u]", (per_group > 1 ? w % per_group : w) ? "," : "",
+           where[2 * w], where[2 * w + 1]);
+    if (per_group > 1 && w % per_group == per_group - 1) printf("]");
+  }
+  printf("],");
+}
+
 void print_report(const Options& o, const Report& r, int code, double wall_s) {
   const bool hbm_fail = r.mismatch_vectors != 0;
+  size_t mfma_cus = 0, mfma_simds = 0, mx_cus = 0, mx_simds = 0;
+  count_where(r.mfma_where, &mfma_cus, &mfma_simds);
+  count_where(r.mx_where, &mx_cus, &mx_simds);
   std::string failed;
   auto add_failed = [&](const char* name) {
     failed += failed.empty() ? "\"" : ",\"";
@@ -1252,8 +1833,10 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
   if (!strcmp(r.copy, "fail")) add_failed("copy");
   if (!strcmp(r.mfma, "fail")) add_failed("mfma");
   if (!strcmp(r.mx, "fail")) add_failed("mx");
+  if (!strcmp(r.lds, "fail")) add_failed("lds");
   if (!strcmp(r.bandwidth, "fail")) add_failed("bandwidth");
   if (!strcmp(r.mx_rate, "fail")) add_failed("mx_rate");
+  if (lds_coverage_required_and_partial(o, r)) add_failed("lds_coverage");
 
   printf("{\"tool\":\"gpucheck\",\"mode\":\"%s\",\"device\":\"%s\","
          "\"compute_units\":%d,\"ok\":%s,\"exit_code\":%d,"
@@ -1322,9 +1905,14 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
          r.mx, r.mx_waves, r.mx_rate);
   for (int f = 0; f < gpucheck::kMxFormats; ++f)
     printf("%s\"%s\":{\"bad_waves\":%ld,\"first_bad_wave\":%ld,"
-           "\"tflops\":%.3f}",
+           "\"first_bad_where\":\"%s\",\"tflops\":%.3f}",
            f ? "," : "", gpucheck::kMxFormatTable[f].name,
            r.mx_formats[f].bad_waves, r.mx_formats[f].first_bad_wave,
+           r.mx_formats[f].first_bad_wave < 0
+               ? ""
+               : where_of(r.mx_where, f * r.mx_waves +
+                                          r.mx_formats[f].first_bad_wave)
+                     .c_str(),
            r.mx_formats[f].tflops);
   printf("},");
   if (o.dump_mx_wave >= 0) {
@@ -1337,6 +1925,54 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
     } else {
       printf("\"mx_tile\":null,");
     }
+  }
+  printf("\"mfma_cus_covered\":%zu,\"mfma_simds_covered\":%zu,"
+         "\"mfma_first_bad_where\":\"%s\",\"mx_cus_covered\":%zu,"
+         "\"mx_simds_covered\":%zu,",
+         mfma_cus, mfma_simds,
+         where_of(r.mfma_where, r.mfma_first_bad_wave).c_str(), mx_cus,
+         mx_simds);
+  printf("\"lds\":\"%s\",", r.lds);
+  if (!r.lds_skip_reason.empty())
+    printf("\"lds_skipped_reason\":\"%s\",",
+           json_escape(r.lds_skip_reason).c_str());
+  printf("\"lds_groups\":%ld,\"lds_rounds\":%u,\"lds_launches\":%ld,"
+         "\"lds_bytes_per_cu\":%d,\"lds_cus_covered\":%zu,"
+         "\"lds_coverage\":\"%s\",\"lds_bad_groups\":%ld,\"lds_bad_cus\":[",
+         r.lds_groups, o.lds_rounds, r.lds_launches, gpucheck::kLdsBytes,
+         r.lds_cus.size(), lds_coverage_full(r) ? "full" : "partial",
+         r.lds_bad_groups);
+  size_t listed = 0;
+  for (const auto& kv : r.lds_bad_cus) {
+    if (listed == kMaxLdsBadCus) break;
+    const Report::LdsBadCu& cu = kv.second;
+    printf("%s{\"where\":\"%s\",\"key\":%u,\"bad_vectors\":%llu,"
+           "\"first_bad_offset\":%llu,\"first_bad_xor\":\"%s\","
+           "\"round\":%llu,\"pass\":%llu}",
+           listed++ ? "," : "", where_name(kv.first).c_str(), kv.first,
+           static_cast<unsigned long long>(cu.bad_vectors),
+           16 * (cu.first & 0x3FFF), hex128(cu.first_xor).c_str(),
+           cu.first >> 15, (cu.first >> 14) & 1);
+  }
+  printf("],\"lds_gbs\":%.3f,", r.lds_gbs);
+  if (o.dump_lds) {
+    if (r.lds_dump_valid) {
+      printf("\"lds_dump\":{\"group\":%u,\"round\":%u,\"pass\":%u,"
+             "\"fnv64\":\"%016llx\",\"same_wave_reads\":%ld,\"vectors\":{",
+             o.dump_lds_group, o.dump_lds_round, o.dump_lds_pass,
+             static_cast<unsigned long long>(r.lds_dump_fnv64),
+             r.lds_dump_same_wave_reads);
+      for (size_t i = 0; i < r.lds_dump_vectors.size(); ++i)
+        printf("%s\"%d\":\"%s\"", i ? "," : "", kLdsDumpVectors[i],
+               r.lds_dump_vectors[i].c_str());
+      printf("}},");
+    } else {
+      printf("\"lds_dump\":null,");
+    }
+  }
+  if (o.dump_lds_where) {
+    print_where_list("lds_where", r.lds_where, 4);
+    print_where_list("mfma_where", r.mfma_where, 1);
   }
   printf("\"wall_s\":%.4f}\n", wall_s);
   fflush(stdout);
@@ -1356,6 +1992,8 @@ int main(int argc, char** argv) {
       if (int rc = check_mfma_args(o, nwaves)) return rc;
       const long mx_waves = o.mx_waves > 0 ? o.mx_waves : 0;
       if (int rc = check_mx_args(o, mx_waves)) return rc;
+      const long lds_groups = o.lds_groups > 0 ? o.lds_groups : 0;
+      if (int rc = check_lds_args(o, lds_groups)) return rc;
       CpuBackend be(o);
       if (be.mem == nullptr) {
         fprintf(stderr, "gpucheck: cannot allocate %zu bytes\n", o.bytes);
@@ -1364,6 +2002,7 @@ int main(int argc, char** argv) {
       run_hbm(be, o, &rep);
       if (nwaves > 0) run_mfma_cpu(o, nwaves, &rep);
       if (mx_waves > 0) run_mx_cpu(o, mx_waves, &rep);
+      if (lds_groups > 0) run_lds_cpu(o, lds_groups, &rep);
     } else {
       int count = 0;
       HIP_CHECK(hipGetDeviceCount(&count));
@@ -1383,6 +2022,9 @@ int main(int argc, char** argv) {
         if (o.mfma_waves > 0) mx_waves = std::min(mx_waves, o.mfma_waves);
       }
       if (int rc = check_mx_args(o, mx_waves)) return rc;
+      const long lds_groups =
+          o.lds_groups >= 0 ? o.lds_groups : 2L * prop.multiProcessorCount;
+      if (int rc = check_lds_args(o, lds_groups)) return rc;
       {
         GpuBackend be(o);
         run_hbm(be, o, &rep);
@@ -1390,6 +2032,7 @@ int main(int argc, char** argv) {
       }
       run_mfma(o, nwaves, &rep);
       if (mx_waves > 0) run_mx(o, mx_waves, prop.multiProcessorCount, &rep);
+      if (lds_groups > 0) run_lds(o, lds_groups, prop, &rep);
     }
   } catch (const HipError& e) {
     fprintf(stderr, "gpucheck: %s\n", e.what.c_str());
@@ -1405,8 +2048,10 @@ int main(int argc, char** argv) {
   else if (!strcmp(rep.copy, "fail")) code = 23;
   else if (!strcmp(rep.mfma, "fail")) code = 21;
   else if (!strcmp(rep.mx, "fail")) code = 24;
+  else if (!strcmp(rep.lds, "fail")) code = 26;
   else if (!strcmp(rep.bandwidth, "fail")) code = 22;
   else if (!strcmp(rep.mx_rate, "fail")) code = 25;
+  else if (lds_coverage_required_and_partial(o, rep)) code = 27;
   const double wall_s =
       std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   print_report(o, rep, code, wall_s);

@@ -164,4 +164,19 @@ GPUCHECK_HD inline uint32_t mx_scale_byte(uint64_t key, int rc, int block) {
                     3u);
 }
 
+// LDS self-test: one workgroup fills a compute unit's whole 160 KiB LDS with
+// 10240 16-byte vectors. Vector i of workgroup `group` in `round` and `pass`
+// holds pattern(lds_key(seed, group, round), pass, i), so an odd pass is the
+// complement of the even one and every address has its own value: an
+// aliased address bit (the 64 KiB line is vector 4096) cannot read back right.
+constexpr int kLdsVectors = 10240;
+constexpr int kLdsBytes = 16 * kLdsVectors;
+
+// Bit 41 keeps these keys apart from mfma_key's and mx_key's.
+GPUCHECK_HD inline uint64_t lds_key(uint64_t seed, uint32_t group,
+                                    uint32_t round) {
+  return mix64(seed ^ mix64((1ull << 41) |
+                            (static_cast<uint64_t>(round) << 20) | group));
+}
+
 }  // namespace gpucheck

@@ -104,6 +104,18 @@ gpu_check_mx_tflops = Gauge("amdvk_gpu_check_mx_tflops",
                             "Block-scaled MX MFMA rate of the last self-test "
                             "(TFLOP/s)",
                             ["gpu", "format"], registry=registry)
+gpu_check_lds_cus_covered = Gauge("amdvk_gpu_check_lds_cus_covered",
+                                  "Compute units whose LDS the last self-test "
+                                  "covered",
+                                  ["gpu"], registry=registry)
+gpu_check_lds_bad_cus = Gauge("amdvk_gpu_check_lds_bad_cus",
+                              "Compute units with an LDS mismatch in the last "
+                              "self-test (the binary lists at most 8)",
+                              ["gpu"], registry=registry)
+gpu_check_mfma_simds_covered = Gauge("amdvk_gpu_check_mfma_simds_covered",
+                                     "SIMDs that ran an MFMA tile in the last "
+                                     "self-test",
+                                     ["gpu"], registry=registry)
 gpu_check_timestamp = Gauge("amdvk_gpu_check_timestamp_seconds",
                             "Unix time of the last self-test",
                             ["gpu"], registry=registry)
@@ -128,6 +140,17 @@ def observe_gpu_check(index: int, result, verdict_ok: bool) -> None:
             value = got.get("tflops") if isinstance(got, dict) else None
             if isinstance(value, (int, float)):
                 gpu_check_mx_tflops.labels(label, str(name)).set(value)
+    # A run without the stage (off, or an older binary) sets nothing.
+    if result.data.get("lds") in ("pass", "fail"):
+        covered = result.data.get("lds_cus_covered")
+        if isinstance(covered, int):
+            gpu_check_lds_cus_covered.labels(label).set(covered)
+        bad = result.data.get("lds_bad_cus")
+        if isinstance(bad, list):
+            gpu_check_lds_bad_cus.labels(label).set(len(bad))
+    simds = result.data.get("mfma_simds_covered")
+    if result.data.get("mfma") in ("pass", "fail") and isinstance(simds, int):
+        gpu_check_mfma_simds_covered.labels(label).set(simds)
 
 
 def render() -> bytes:
