@@ -84,6 +84,15 @@ def build_parser() -> argparse.ArgumentParser:
                    metavar="FORMAT:X",
                    help="fail a check whose MX rate for FORMAT (fp8, bf8, "
                         "fp4, fp8xfp4) is below X TFLOP/s; repeatable")
+    p.add_argument("--no-gpu-check-dense", dest="gpu_check_dense",
+                   action="store_false", default=None,
+                   help="skip the dense-format (F16/BF16/FP8/BF8/INT8/F32/"
+                        "F64) stage")
+    p.add_argument("--gpu-check-min-dense-tflops", action="append",
+                   default=None, metavar="FORMAT:X",
+                   help="fail a check whose dense rate for FORMAT (f16, "
+                        "bf16x16, fp8, bf8, i8, f32, f64) is below X "
+                        "TFLOP/s; repeatable")
     p.add_argument("--no-gpu-check-lds", dest="gpu_check_lds",
                    action="store_false", default=None,
                    help="skip the per-CU LDS stage")
@@ -99,18 +108,31 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def _parse_floors(values, base, formats, flag) -> dict:
+    floors = dict(base or {})
+    for value in values:
+        name, sep, floor = value.partition(":")
+        if not sep or name not in formats:
+            raise SystemExit(f"{flag} {value!r}: expected "
+                             f"FORMAT:X with FORMAT one of {list(formats)}")
+        floors[name] = float(floor)
+    return floors
+
+
 def parse_mx_floors(values, base=None) -> dict:
     """["fp4:4000", ...] laid over ``base`` -> {format: TFLOP/s floor}."""
     from .gpu.diagnostics import MX_FORMATS
 
-    floors = dict(base or {})
-    for value in values:
-        name, sep, floor = value.partition(":")
-        if not sep or name not in MX_FORMATS:
-            raise SystemExit(f"--gpu-check-min-mx-tflops {value!r}: expected "
-                             f"FORMAT:X with FORMAT one of {list(MX_FORMATS)}")
-        floors[name] = float(floor)
-    return floors
+    return _parse_floors(values, base, MX_FORMATS,
+                         "--gpu-check-min-mx-tflops")
+
+
+def parse_dense_floors(values, base=None) -> dict:
+    """The same for ``--gpu-check-min-dense-tflops``."""
+    from .gpu.diagnostics import DENSE_FORMATS
+
+    return _parse_floors(values, base, DENSE_FORMATS,
+                         "--gpu-check-min-dense-tflops")
 
 
 def validate_environment() -> None:
@@ -170,6 +192,11 @@ def main(argv=None) -> int:
     if args.gpu_check_min_mx_tflops is not None:
         cfg.gpu_check_min_mx_tflops = parse_mx_floors(
             args.gpu_check_min_mx_tflops, cfg.gpu_check_min_mx_tflops)
+    if args.gpu_check_dense is not None:
+        cfg.gpu_check_dense = args.gpu_check_dense
+    if args.gpu_check_min_dense_tflops is not None:
+        cfg.gpu_check_min_dense_tflops = parse_dense_floors(
+            args.gpu_check_min_dense_tflops, cfg.gpu_check_min_dense_tflops)
     if args.gpu_check_lds is not None:
         cfg.gpu_check_lds = args.gpu_check_lds
     if args.gpu_check_lds_require_coverage:

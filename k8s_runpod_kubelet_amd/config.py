@@ -130,6 +130,10 @@ class Config:
     gpu_check_mx: bool = True              # run the MX (FP8/BF8/FP4) stage
     # MX rate floors in TFLOP/s by format (fp8, bf8, fp4, fp8xfp4); empty = off
     gpu_check_min_mx_tflops: Dict[str, float] = field(default_factory=dict)
+    gpu_check_dense: bool = True           # run the dense-format stage
+    # dense rate floors in TFLOP/s by format (f16, bf16x16, fp8, bf8, i8,
+    # f32, f64); empty = off
+    gpu_check_min_dense_tflops: Dict[str, float] = field(default_factory=dict)
     gpu_check_lds: bool = True             # run the per-CU LDS stage
     # fail a check that did not reach every compute unit's LDS
     gpu_check_lds_require_coverage: bool = False
@@ -168,6 +172,24 @@ def load_config(path: Optional[str]) -> Config:
     if not isinstance(cfg.gpu_check_min_mx_tflops, dict):
         raise ValueError(f"provider config {path!r}: gpu_check_min_mx_tflops "
                          f"must map a format to a floor")
+    if cfg.gpu_check_min_dense_tflops is None:
+        cfg.gpu_check_min_dense_tflops = {}
+    if not isinstance(cfg.gpu_check_min_dense_tflops, dict):
+        raise ValueError(f"provider config {path!r}: "
+                         f"gpu_check_min_dense_tflops must map a format to a "
+                         f"floor")
+    # Beyond the MX floors' check above: an unknown dense format or a floor
+    # that is no number is refused here, at load, not at the first check.
+    # (The MX floors keep their released behaviour: those surface as the
+    # manager's ValueError when a check builds its arguments.) Imported here
+    # as cli.py does, since gpu.diagnostics is not needed to load a config.
+    from .gpu.diagnostics import dense_floor_args
+
+    try:
+        dense_floor_args(cfg.gpu_check_min_dense_tflops)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"provider config {path!r}: "
+                         f"gpu_check_min_dense_tflops: {exc}") from exc
     if cfg.datacenter_ids is None:
         cfg.datacenter_ids = []
     if isinstance(cfg.datacenter_ids, str):

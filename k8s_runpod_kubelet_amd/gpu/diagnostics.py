@@ -5,9 +5,10 @@ see a GPU that still enumerates but no longer stores bits or multiplies
 matrices. ``gpucheck`` (ops/gpucheck/gpucheck.hip) runs real work on an idle
 GPU — an HBM pattern fill/verify, a copy-bandwidth measurement, an exact
 MFMA self-test, an exact self-test of the block-scaled MX (FP8/BF8/FP4)
-matrix path and a per-CU LDS self-test that names the compute unit of a
-fault — and this module turns its verdict into the per-GPU schedulability
-gate.
+matrix path, a per-CU LDS self-test that names the compute unit of a
+fault and an exact self-test of the dense matrix formats (F16, BF16 16x16,
+FP8, BF8, INT8, F32, F64) with their rates — and this module turns its
+verdict into the per-GPU schedulability gate.
 
 The binary always runs as a fresh child process scoped to one GPU, exactly
 like a pod (``device_env``); the kubelet process itself never opens the GPU.
@@ -35,8 +36,9 @@ log = logging.getLogger("gpu.diagnostics")
 # gpucheck exit codes (ops/gpucheck/gpucheck.hip)
 EXIT_STAGES = {2: "usage", 11: "hip", 20: "hbm", 21: "mfma", 22: "bandwidth",
                23: "copy", 24: "mx", 25: "mx_rate", 26: "lds",
-               27: "lds_coverage"}
+               27: "lds_coverage", 28: "dense", 29: "dense_rate"}
 MX_FORMATS = ("fp8", "bf8", "fp4", "fp8xfp4")
+DENSE_FORMATS = ("f16", "bf16x16", "fp8", "bf8", "i8", "f32", "f64")
 RESERVATION_PREFIX = "amdvk-system/gpucheck-"
 
 
@@ -54,7 +56,8 @@ class GpuCheckResult:
     ok: bool
     exit_code: Optional[int] = None
     # "" on a pass; otherwise the failing stage ("hbm", "copy", "mfma",
-    # "mx", "lds", "bandwidth", "mx_rate", "lds_coverage", "hip", "usage")
+    # "mx", "lds", "dense", "bandwidth", "mx_rate", "dense_rate",
+    # "lds_coverage", "hip", "usage")
     # or "timeout", "signal N", "bad-output".
     reason: str = ""
     data: Dict[str, Any] = field(default_factory=dict)  # the binary's JSON
@@ -74,21 +77,30 @@ class GpuCheckResult:
         return out
 
 
+def _floor_args(floors, formats, flag: str, what: str) -> List[str]:
+    floors = dict(floors or {})
+    unknown = sorted(set(floors) - set(formats))
+    if unknown:
+        raise ValueError(f"unknown {what} format(s) {unknown}; "
+                         f"expected {list(formats)}")
+    out: List[str] = []
+    for name in formats:
+        floor = float(floors.get(name) or 0.0)
+        if floor > 0:
+            out += [flag, f"{name}:{floor!r}"]
+    return out
+
+
 def mx_floor_args(floors) -> List[str]:
     """{format: TFLOP/s floor} -> ``--min-mx-tflops`` flags, in the binary's
     format order; floors of 0 are off. Raises ``ValueError`` for an unknown
     format."""
-    floors = dict(floors or {})
-    unknown = sorted(set(floors) - set(MX_FORMATS))
-    if unknown:
-        raise ValueError(f"unknown MX format(s) {unknown}; "
-                         f"expected {list(MX_FORMATS)}")
-    out: List[str] = []
-    for name in MX_FORMATS:
-        floor = float(floors.get(name) or 0.0)
-        if floor > 0:
-            out += ["--min-mx-tflops", f"{name}:{floor!r}"]
-    return out
+    return _floor_args(floors, MX_FORMATS, "--min-mx-tflops", "MX")
+
+
+def dense_floor_args(floors) -> List[str]:
+    """The same for the dense formats and ``--min-dense-tflops``."""
+    return _floor_args(floors, DENSE_FORMATS, "--min-dense-tflops", "dense")
 
 
 def first_bad_mx(data: Dict[str, Any]) -> str:
@@ -99,6 +111,20 @@ def first_bad_mx(data: Dict[str, Any]) -> str:
         for name, got in formats.items():
             if isinstance(got, dict) and got.get("bad_waves"):
                 return f"{name} wave {got.get('first_bad_wave')}"
+    return ""
+
+
+def first_bad_dense(data: Dict[str, Any]) -> str:
+    """"i8 wave 17 on xcc2.se1.sh0.cu5" for the first dense format with a
+    bad wave in the binary's JSON (without the compute unit where the binary
+    names none), or ""."""
+    formats = data.get("dense_formats")
+    if isinstance(formats, dict):
+        for name, got in formats.items():
+            if isinstance(got, dict) and got.get("bad_waves"):
+                where = got.get("first_bad_where")
+                return (f"{name} wave {got.get('first_bad_wave')}"
+                        + (f" on {where}" if where else ""))
     return ""
 
 
@@ -223,6 +249,11 @@ class DiagnosticsManager:
         else:
             args += mx_floor_args(
                 getattr(self.config, "gpu_check_min_mx_tflops", None))
+        if not getattr(self.config, "gpu_check_dense", True):
+            args += ["--dense-waves", "0"]
+        else:
+            args += dense_floor_args(
+                getattr(self.config, "gpu_check_min_dense_tflops", None))
         if not getattr(self.config, "gpu_check_lds", True):
             args += ["--lds-groups", "0"]
         if getattr(self.config, "gpu_check_lds_require_coverage", False):
@@ -301,9 +332,12 @@ class DiagnosticsManager:
                 "metadata": {"name": self.node_name, "namespace": "default"}}
         where = first_bad_mx(result.data) if result.reason == "mx" else ""
         lds = first_bad_lds(result.data) if result.reason == "lds" else ""
+        dense = (first_bad_dense(result.data) if result.reason == "dense"
+                 else "")
         message = (f"GPU {idx} failed self-test: stage={result.reason} "
                    + (f"first_bad_mx={where} " if where else "")
-                   + (f"lds: {lds} " if lds else "") +
+                   + (f"lds: {lds} " if lds else "")
+                   + (f"first_bad_dense={dense} " if dense else "") +
                    f"first_bad_offset={result.data.get('first_bad_offset')} "
                    f"mismatch_vectors={result.data.get('mismatch_vectors')}; "
                    f"GPU fenced until an operator re-check passes")
@@ -408,7 +442,8 @@ def main(argv=None) -> int:
         description="Run the active GPU self-test on one GPU and print its "
                     "JSON. Exits with the gpucheck exit code (0 pass, 20 HBM, "
                     "23 copy mismatch, 21 MFMA, 24 MX mismatch, 26 LDS "
-                    "mismatch, 22 bandwidth, 25 MX rate below its floor, "
+                    "mismatch, 28 dense mismatch, 22 bandwidth, 25 MX rate "
+                    "below its floor, 29 dense rate below its floor, "
                     "27 LDS coverage partial, 11 HIP error; 1 for a "
                     "timeout, signal or unparsable output).")
     p.add_argument("--gpu", type=int, required=True)
@@ -419,6 +454,11 @@ def main(argv=None) -> int:
                    metavar="FORMAT:X",
                    help="fail if the MX rate of FORMAT (fp8, bf8, fp4, "
                         "fp8xfp4) is below X TFLOP/s; repeatable")
+    p.add_argument("--min-dense-tflops", action="append", default=[],
+                   metavar="FORMAT:X",
+                   help="fail if the dense rate of FORMAT (f16, bf16x16, "
+                        "fp8, bf8, i8, f32, f64) is below X TFLOP/s; "
+                        "repeatable")
     p.add_argument("--no-lds", action="store_true",
                    help="skip the per-CU LDS stage")
     p.add_argument("--lds-require-coverage", action="store_true",
@@ -438,6 +478,8 @@ def main(argv=None) -> int:
         extra += ["--min-copy-gbs", repr(args.min_copy_gbs)]
     for floor in args.min_mx_tflops:
         extra += ["--min-mx-tflops", floor]
+    for floor in args.min_dense_tflops:
+        extra += ["--min-dense-tflops", floor]
     if args.no_lds:
         extra += ["--lds-groups", "0"]
     if args.lds_require_coverage:

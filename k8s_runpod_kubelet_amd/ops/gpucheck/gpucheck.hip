@@ -1,7 +1,7 @@
 // gpucheck — active GPU self-test run between tenants.
 //
 // Tests visible device 0 (the caller scopes visibility with
-// ROCR_VISIBLE_DEVICES) in five stages:
+// ROCR_VISIBLE_DEVICES) in six stages:
 //   1. HBM fill + verify with a hashed 16-byte pattern and its complement,
 //   2. device-to-device copy bandwidth, with the copied half verified against
 //      the pattern its source holds,
@@ -12,15 +12,20 @@
 //   5. an LDS self-test: workgroups that each hold a compute unit's whole
 //      160 KiB LDS fill it with the hashed pattern and its complement and
 //      read it back from another wave; the host counts which compute units
-//      were covered and names the compute unit of a mismatch.
-// Every wave of stages 3 to 5 records where it ran (XCC, shader engine,
+//      were covered and names the compute unit of a mismatch,
+//   6. an exact self-test of the dense (non-scaled) matrix formats, one
+//      instruction each: f16 and fp8/bf8 32x32x16, bf16 16x16x32, i8
+//      32x32x32 (i32 accumulators), f32 32x32x2 and f64 16x16x4, and the
+//      measured rate of each.
+// Every wave of stages 3 to 6 records where it ran (XCC, shader engine,
 // shader array, compute unit, SIMD), so coverage is reported and a bad wave
 // is located in the hardware.
 // Prints exactly one JSON object as the last stdout line and exits with a
 // stage-specific code (the first that applies, in this order):
 //   0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, 23 copy mismatch,
-//   21 MFMA mismatch, 24 MX mismatch, 26 LDS mismatch, 22 copy bandwidth
-//   below --min-copy-gbs, 25 an MX rate below its --min-mx-tflops, 27 LDS
+//   21 MFMA mismatch, 24 MX mismatch, 26 LDS mismatch, 28 dense mismatch,
+//   22 copy bandwidth below --min-copy-gbs, 25 an MX rate below its
+//   --min-mx-tflops, 29 a dense rate below its --min-dense-tflops, 27 LDS
 //   coverage partial under --lds-require-coverage.
 // `--cpu` runs the HBM stage as host loops over malloc'ed memory and makes no
 // HIP call, so the CLI, JSON and mismatch localisation are testable without
@@ -29,14 +34,16 @@
 // explicit --mx-waves it does the same for the MX tiles (rates stay 0 and
 // their floors are ignored), and with an explicit --lds-groups it runs the
 // LDS stage's write order, rotated read, injection and judging over a host
-// buffer per group, reporting compute unit `group % 5` for every wave.
+// buffer per group, reporting compute unit `group % 5` for every wave, and
+// with an explicit --dense-waves it fills the dense tiles from the host
+// integer product and judges them (rates stay 0, floors are ignored).
 //
 // Flags that exist for the test suite: --dump-pattern, --dump-vectors,
 // --store-variant, --inject-flip, --inject-pass, --inject-copy-flip,
 // --dump-mfma-tile, --inject-mfma, --dump-mx-tile, --inject-mx, --dump-lds,
-// --dump-lds-where, --inject-lds. The injections flip bits in the region or
-// in the LDS, or change the host copy of the MFMA or MX result; they test
-// the checkers.
+// --dump-lds-where, --inject-lds, --dump-dense-tile, --inject-dense. The
+// injections flip bits in the region or in the LDS, or change the host copy
+// of the MFMA, MX or dense result; they test the checkers.
 //
 // Build: hipcc --offload-arch=gfx950 -O2 -std=c++17 gpucheck.hip -o gpucheck
 
@@ -54,6 +61,7 @@
 #include <map>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -83,6 +91,7 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 constexpr int kBlock = 256;
 constexpr size_t kMaxGrid = 2048;
 constexpr uint64_t kNoBad = ~0ull;
+constexpr long long kDenseNotAnInteger = INT64_MIN;  // below every exact value
 constexpr size_t kCacheResidentBelow = 512ull << 20;
 
 // ---------------------------------------------------------------- kernels
@@ -391,6 +400,211 @@ __global__ __launch_bounds__(kBlock) void mx_rate(float* __restrict__ sink,
   sink[tid] = sum;
 }
 
+// ------------------------------------------------------- dense formats
+//
+// One instruction per format (gpucheck::kDenseFormatTable):
+//   f16      v_mfma_f32_32x32x16_f16       bf16x16  v_mfma_f32_16x16x32_bf16
+//   fp8      v_mfma_f32_32x32x16_fp8_fp8   bf8      v_mfma_f32_32x32x16_bf8_bf8
+//   i8       v_mfma_i32_32x32x32_i8        f32      v_mfma_f32_32x32x2_f32
+//   f64      v_mfma_f64_16x16x4_f64
+//
+// How the kernels fill the operands, one rule for all seven. With mn the
+// tile side, lane l has rc = l & (mn - 1) and g = l / mn (g = 0, 1 for 32x32,
+// 0..3 for 16x16), and holds per = step_k . mn / 64 elements of row rc of A
+// and of column rc of B per instruction (8 f16, bf16, fp8 or bf8 values; 16
+// int8; one f32 or f64). Into slot (g, j) of step s, element j of the lane's
+// fragment (16-bit elements in ascending halves of the dwords, 8-bit elements
+// in ascending bytes), both A and B put k = step_k . s + per . g + j.
+//
+// That k is THIS KERNEL'S LABELLING of the slots, not the instruction's
+// documented k order: do not load real A or B data from memory by it. A sum
+// over k is the same for any order that A and B share, so a product cannot
+// see which k of a step the hardware takes a slot for (for bf16, f32 and f64
+// the labelling happens to be the documented map; for f16, the 8-bit floats
+// and i8 nothing here says so). What the tiles, which on an MI355X equal the
+// independent reference for every format, do fix: the row of A and the
+// column of B sit on lane & (mn - 1), and the instruction multiplies slot
+// (g, j) of A with slot (g, j) of B, for 8 and 16 bytes per lane as for bf16.
+//
+// C/D map: 32x32 forms, register v is row (v & 3) + 8 (v >> 2) + 4 g; the
+// 16x16 f32-accumulator form, row 4 g + v; f64, row g + 4 v. Column rc.
+template <int kFmt>
+struct DenseTypes {
+  static constexpr gpucheck::DenseFormat fmt = gpucheck::kDenseFormatTable[kFmt];
+  static constexpr int regs = fmt.mn * fmt.mn / 64;
+  static constexpr int per = fmt.step_k * fmt.mn / 64;
+  // What a lane stores per result: i32 for i8, f64 for f64, else f32.
+  using Elem = std::conditional_t<
+      kFmt == gpucheck::kDenseI8, int,
+      std::conditional_t<kFmt == gpucheck::kDenseF64, double, float>>;
+  typedef Elem Acc __attribute__((ext_vector_type(regs)));
+};
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// One lane's elements of one instruction: element j hashes index
+// first + j . stride (stride 1 along a row of A, mn down a column of B).
+template <int kFmt, bool kNonZero>
+__device__ inline auto dense_fragment(uint64_t key, uint32_t first,
+                                      uint32_t stride) {
+  using namespace gpucheck;
+  constexpr int per = DenseTypes<kFmt>::per;
+  auto hash = [&](int j) { return mix64(key + first + j * stride); };
+  auto value = [&](int j) {
+    return kNonZero ? dense_nonzero_int_from_hash(kFmt, hash(j))
+                    : dense_int_from_hash(kFmt, hash(j));
+  };
+  (void)value;  // the 8-bit float formats take codes, not values
+  if constexpr (kFmt == kDenseF16) {
+    f16x8 frag;
+#pragma unroll
+    for (int j = 0; j < per; ++j)
+      frag[j] = static_cast<_Float16>(static_cast<float>(value(j)));
+    return frag;
+  } else if constexpr (kFmt == kDenseBf16x16) {
+    // |value| <= 15 has four significant bits: the top half of its f32 bits
+    // is its bf16, exactly.
+    s16x8 frag;
+#pragma unroll
+    for (int j = 0; j < per; ++j)
+      frag[j] = static_cast<short>(
+          __builtin_bit_cast(uint32_t, static_cast<float>(value(j))) >> 16);
+    return __builtin_bit_cast(bf16x8, frag);
+  } else if constexpr (kFmt == kDenseFp8 || kFmt == kDenseBf8) {
+    uint64_t frag = 0;
+#pragma unroll
+    for (int j = 0; j < per; ++j) {
+      const uint64_t code = kNonZero
+                                ? dense_nonzero_code_from_hash(kFmt, hash(j))
+                                : dense_code_from_hash(kFmt, hash(j));
+      frag |= code << (8 * j);
+    }
+    return static_cast<long>(frag);
+  } else if constexpr (kFmt == kDenseI8) {
+    i32x4 frag;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        word |= (static_cast<uint32_t>(value(4 * d + i)) & 0xFFu) << (8 * i);
+      frag[d] = static_cast<int>(word);
+    }
+    return frag;
+  } else if constexpr (kFmt == kDenseF32) {
+    return static_cast<float>(value(0));
+  } else {
+    return static_cast<double>(value(0));
+  }
+}
+
+template <int kFmt, typename Frag>
+__device__ inline typename DenseTypes<kFmt>::Acc dense_mfma(
+    Frag a, Frag b, typename DenseTypes<kFmt>::Acc acc) {
+  using namespace gpucheck;
+  if constexpr (kFmt == kDenseF16)
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
+  else if constexpr (kFmt == kDenseBf16x16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+  else if constexpr (kFmt == kDenseFp8)
+    return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a, b, acc, 0, 0, 0);
+  else if constexpr (kFmt == kDenseBf8)
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf8_bf8(a, b, acc, 0, 0, 0);
+  else if constexpr (kFmt == kDenseI8)
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
+  else if constexpr (kFmt == kDenseF32)
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+}
+
+// Each wave computes one tile of format kFmt from operands generated in
+// registers and stores it to out[wave][row][col]; lane 0 also stores where
+// the wave ran. The maps are in the comment above.
+template <int kFmt>
+__global__ __launch_bounds__(kBlock) void dense_selftest(
+    typename DenseTypes<kFmt>::Elem* __restrict__ out,
+    uint32_t* __restrict__ where, uint32_t nwaves, uint64_t seed) {
+  using T = DenseTypes<kFmt>;
+  constexpr int mn = T::fmt.mn, K = T::fmt.k, step_k = T::fmt.step_k;
+  const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  // Wave-uniform, as in mfma_selftest: EXEC is full at every MFMA.
+  if (wave >= nwaves) return;
+  const int lane = threadIdx.x & 63;
+  const int rc = lane & (mn - 1);
+  const int g = lane / mn;
+  const uint64_t key_a = gpucheck::dense_key(seed, wave, kFmt, 0);
+  const uint64_t key_b = gpucheck::dense_key(seed, wave, kFmt, 1);
+  typename T::Acc acc;
+  for (int v = 0; v < T::regs; ++v) acc[v] = 0;
+#pragma unroll
+  for (int s = 0; s < K / step_k; ++s) {
+    const int k0 = step_k * s + T::per * g;
+    const auto a = dense_fragment<kFmt, false>(
+        key_a, static_cast<uint32_t>(rc * K + k0), 1);
+    const auto b = dense_fragment<kFmt, false>(
+        key_b, static_cast<uint32_t>(k0 * mn + rc), mn);
+    acc = dense_mfma<kFmt>(a, b, acc);
+  }
+  typename T::Elem* tile = out + static_cast<size_t>(wave) * (mn * mn);
+#pragma unroll
+  for (int v = 0; v < T::regs; ++v) {
+    const int row = mn == 32 ? (v & 3) + 8 * (v >> 2) + 4 * g
+                    : kFmt == gpucheck::kDenseF64 ? g + 4 * v
+                                                  : 4 * g + v;
+    tile[row * mn + rc] = acc[v];
+  }
+  if (lane == 0) store_where(where, wave);
+}
+
+// Timed: every wave issues 4 * trips MFMAs of one format over four
+// independent accumulators (the 16x16 forms' dependent latency exceeds their
+// issue interval), from hashed non-zero operands, and writes one value per
+// lane to sink[global thread] so the work is live. The i8 sums wrap. The
+// timed loop must hold nothing but the MFMAs and its counter (see below).
+template <int kFmt>
+__global__ __launch_bounds__(kBlock) void dense_rate(
+    typename DenseTypes<kFmt>::Elem* __restrict__ sink, uint32_t trips,
+    uint64_t seed) {
+  using T = DenseTypes<kFmt>;
+  const uint32_t tid = blockIdx.x * kBlock + threadIdx.x;
+  const uint64_t key = gpucheck::dense_key(seed, tid >> 6, kFmt, 0);
+  const uint32_t lane = threadIdx.x & 63;
+  const auto a = dense_fragment<kFmt, true>(key, lane * 32, 1);
+  const auto b = dense_fragment<kFmt, true>(key, lane * 32 + 16, 1);
+  typename T::Acc acc0, acc1, acc2, acc3;
+  // Different starting values: four chains the compiler cannot fold into one.
+  for (int v = 0; v < T::regs; ++v) {
+    acc0[v] = 0;
+    acc1[v] = 1;
+    acc2[v] = 2;
+    acc3[v] = 3;
+  }
+  // An empty statement that holds the four accumulators in accumulation
+  // registers before the loop. Without it hipcc keeps the loop-carried values
+  // of the bf16x16 and f64 kernels in VGPRs and copies them to and from the
+  // MFMAs' registers on every trip (8 to 64 moves and the waits they need),
+  // which halves the rate measured. With it the loop of every format is the
+  // four MFMAs, the counter and one s_nop; tests/test_gpucheck_dense_isa.py
+  // holds the compiled loops to that.
+  asm volatile("" : "+a"(acc0), "+a"(acc1), "+a"(acc2), "+a"(acc3));
+  for (uint32_t t = 0; t < trips; ++t) {
+    acc0 = dense_mfma<kFmt>(a, b, acc0);
+    acc1 = dense_mfma<kFmt>(a, b, acc1);
+    acc2 = dense_mfma<kFmt>(a, b, acc2);
+    acc3 = dense_mfma<kFmt>(a, b, acc3);
+  }
+  // Unsigned for i8: the sums wrap, in the accumulators and here.
+  using Sum = std::conditional_t<std::is_same_v<typename T::Elem, int>,
+                                 unsigned int, typename T::Elem>;
+  Sum sum = 0;
+  for (int v = 0; v < T::regs; ++v)
+    sum += static_cast<Sum>(acc0[v]) + static_cast<Sum>(acc1[v]) +
+           static_cast<Sum>(acc2[v]) + static_cast<Sum>(acc3[v]);
+  sink[tid] = static_cast<typename T::Elem>(sum);
+}
+
 // The LDS self-test. One record per workgroup, updated only by waves that
 // saw a mismatch.
 struct LdsRecord {
@@ -559,6 +773,13 @@ struct Options {
   std::vector<MxInject> mx_inject;
   double min_mx_tflops[gpucheck::kMxFormats] = {0, 0, 0, 0};
   uint64_t mx_rate_instr = 65536;  // timed MFMAs per wave and launch
+  // Dense stage. Formats are indices into gpucheck::kDenseFormatTable.
+  long dense_waves = -1;  // -1: 4 x multiProcessorCount, capped by --mfma-waves
+  int dump_dense_format = -1;
+  long dump_dense_wave = -1;
+  std::vector<MxInject> dense_inject;
+  double min_dense_tflops[gpucheck::kDenseFormats] = {0, 0, 0, 0, 0, 0, 0};
+  uint64_t dense_rate_instr = 16384;  // timed MFMAs per wave and launch
   // LDS stage.
   long lds_groups = -1;  // -1: 2 x multiProcessorCount (0 under --cpu)
   uint32_t lds_rounds = 4;
@@ -577,6 +798,7 @@ constexpr size_t kMaxFlips = 16;
 constexpr size_t kMaxDumpVectors = 16;
 constexpr size_t kMaxMfmaInject = 8;
 constexpr size_t kMaxMxInject = 8;
+constexpr size_t kMaxDenseInject = 8;
 const char* const kVariantNames[2] = {"plain", "nontemporal"};
 
 bool parse_u64(const char* s, uint64_t* out, bool allow_suffix) {
@@ -625,6 +847,10 @@ int usage(const char* why, const char* arg) {
           "[--mx-rate-instr N]\n"
           "                (FORMAT: fp8, bf8, fp4 or fp8xfp4; --mx-waves 0 "
           "skips the MX stage)\n"
+          "                [--dense-waves W] [--min-dense-tflops FORMAT:X]... "
+          "[--dense-rate-instr N]\n"
+          "                (FORMAT: f16, bf16x16, fp8, bf8, i8, f32 or f64; "
+          "--dense-waves 0 skips the dense stage)\n"
           "                [--lds-groups N] [--lds-rounds R] "
           "[--lds-max-launches L] [--lds-require-coverage]\n"
           "                (--lds-groups 0 skips the LDS stage)\n"
@@ -638,12 +864,15 @@ int usage(const char* why, const char* arg) {
           "                [--inject-mx FORMAT:WAVE:ELEM]... "
           "[--dump-lds GROUP:ROUND:PASS] [--dump-lds-where]\n"
           "                [--inject-lds GROUP:ROUND:PASS:BYTE:BIT]...\n"
+          "                [--dump-dense-tile FORMAT:WAVE] "
+          "[--inject-dense FORMAT:WAVE:ELEM]...\n"
           "exit: 0 pass, 2 usage, 11 HIP error, 20 HBM mismatch, "
           "23 copy mismatch, 21 MFMA mismatch,\n"
-          "      24 MX mismatch, 26 LDS mismatch, 22 copy bandwidth below "
-          "--min-copy-gbs,\n"
-          "      25 MX rate below --min-mx-tflops, 27 LDS coverage partial "
-          "under --lds-require-coverage\n",
+          "      24 MX mismatch, 26 LDS mismatch, 28 dense mismatch, "
+          "22 copy bandwidth below --min-copy-gbs,\n"
+          "      25 MX rate below --min-mx-tflops, 29 dense rate below "
+          "--min-dense-tflops,\n"
+          "      27 LDS coverage partial under --lds-require-coverage\n",
           why, arg ? " " : "", arg ? arg : "");
   return 2;
 }
@@ -678,6 +907,21 @@ int parse_mx_format(const char* v, const char** rest) {
   for (int f = 0; f < gpucheck::kMxFormats; ++f)
     if (name == gpucheck::kMxFormatTable[f].name) return f;
   return -1;
+}
+
+// The same for the dense formats.
+int parse_dense_format(const char* v, const char** rest) {
+  const char* colon = v ? strchr(v, ':') : nullptr;
+  if (colon == nullptr) return -1;
+  const std::string name(v, colon - v);
+  *rest = colon + 1;
+  for (int f = 0; f < gpucheck::kDenseFormats; ++f)
+    if (name == gpucheck::kDenseFormatTable[f].name) return f;
+  return -1;
+}
+
+int dense_tile_elems(int f) {
+  return gpucheck::kDenseFormatTable[f].mn * gpucheck::kDenseFormatTable[f].mn;
 }
 
 // Returns 0 on success, 2 on a usage error.
@@ -792,6 +1036,37 @@ int parse_args(int argc, char** argv, Options* o) {
       if (!parse_u64(next(), &u, false) || u == 0 || u > (1ull << 30))
         return usage("bad value for", "--mx-rate-instr");
       o->mx_rate_instr = u;
+    } else if (a == "--dense-waves") {
+      if (!parse_u64(next(), &u, false) || u > 65536)
+        return usage("bad value for", "--dense-waves");
+      o->dense_waves = static_cast<long>(u);
+    } else if (a == "--dump-dense-tile") {
+      const char* rest = nullptr;
+      const int f = parse_dense_format(next(), &rest);
+      if (f < 0 || !parse_u64(rest, &u, false) || u >= 65536)
+        return usage("bad value for", "--dump-dense-tile");
+      o->dump_dense_format = f;
+      o->dump_dense_wave = static_cast<long>(u);
+    } else if (a == "--inject-dense") {
+      const char* rest = nullptr;
+      uint64_t elem = 0;
+      const int f = parse_dense_format(next(), &rest);
+      if (f < 0 || !parse_pair(rest, &u, &elem) || u >= 65536 ||
+          elem >= static_cast<uint64_t>(dense_tile_elems(f)))
+        return usage("bad value for", "--inject-dense");
+      if (o->dense_inject.size() == kMaxDenseInject)
+        return usage("too many", "--inject-dense");
+      o->dense_inject.push_back(
+          {f, static_cast<long>(u), static_cast<int>(elem)});
+    } else if (a == "--min-dense-tflops") {
+      const char* rest = nullptr;
+      const int f = parse_dense_format(next(), &rest);
+      if (f < 0 || !parse_double(rest, &o->min_dense_tflops[f]))
+        return usage("bad value for", "--min-dense-tflops");
+    } else if (a == "--dense-rate-instr") {
+      if (!parse_u64(next(), &u, false) || u == 0 || u > (1ull << 30))
+        return usage("bad value for", "--dense-rate-instr");
+      o->dense_rate_instr = u;
     } else if (a == "--lds-groups") {
       if (!parse_u64(next(), &u, false) || u > 65536)
         return usage("bad value for", "--lds-groups");
@@ -875,6 +1150,16 @@ int check_mx_args(const Options& o, long nwaves) {
   return 0;
 }
 
+// The same for the dense flags.
+int check_dense_args(const Options& o, long nwaves) {
+  if (o.dump_dense_wave >= nwaves)
+    return usage("--dump-dense-tile wave is outside the run", nullptr);
+  for (const Options::MxInject& m : o.dense_inject)
+    if (m.wave >= nwaves)
+      return usage("--inject-dense wave is outside the run", nullptr);
+  return 0;
+}
+
 // The same for the LDS flags: they name workgroups and rounds of the run.
 int check_lds_args(const Options& o, long groups) {
   if (o.dump_lds && (o.dump_lds_group >= groups || o.dump_lds_round >= o.lds_rounds))
@@ -933,6 +1218,22 @@ struct Report {
   // Where the MFMA and MX waves ran: [cu key, simd] per wave (MX: per format
   // and wave). Empty under --cpu.
   std::vector<uint32_t> mfma_where, mx_where;
+  double mx_s = 0;  // wall time of the MX stage, host product included
+  // Dense
+  int clock_mhz = 0;  // the device's reported clock; 0 under --cpu
+  const char* dense = "skipped";
+  const char* dense_rate = "skipped";
+  long dense_waves = 0;
+  struct DenseFormatResult {
+    long bad_waves = 0, first_bad_wave = -1;
+    double tflops = 0, launch_ms = 0;
+  };
+  DenseFormatResult dense_formats[gpucheck::kDenseFormats];
+  // Values times the format's scale; kDenseNotAnInteger where that is none.
+  std::vector<long long> dense_tile;
+  // [cu key, simd] per format and wave, format-major. Empty under --cpu.
+  std::vector<uint32_t> dense_where;
+  double dense_s = 0;  // wall time of the dense stage
   // LDS
   const char* lds = "skipped";
   std::string lds_skip_reason;
@@ -1579,6 +1880,208 @@ void run_mx(const Options& o, long nwaves, int compute_units, Report* rep) {
       rep->mx_rate = "fail";
 }
 
+// ------------------------------------------------------------ dense stage
+
+// The tile wave `w` must produce in format `f`, times the format's scale,
+// row-major: an integer matrix product. The operands of fp8 and bf8 are
+// decoded from their codes and held times 2 (exact: multiples of 1/2), so
+// their product is in quarter-units. The arithmetic is floating point that
+// holds these integers exactly, by the bounds in gpucheck_pattern.h: Acc is
+// float below 2^24 (all but f64) and double below 2^53 for f64. As in
+// mx_expected_tile, the loop order keeps the inner loop free of a reduction.
+template <typename Acc>
+void dense_expected_tile_as(int f, uint64_t seed, long w, double* out) {
+  using namespace gpucheck;
+  const DenseFormat& fmt = kDenseFormatTable[f];
+  const int mn = fmt.mn, K = fmt.k;
+  const uint64_t key_a = dense_key(seed, static_cast<uint32_t>(w), f, 0);
+  const uint64_t key_b = dense_key(seed, static_cast<uint32_t>(w), f, 1);
+  // An 8-bit float element depends on kMxHashBits bits of its hash: each
+  // code is generated and decoded once.
+  constexpr uint32_t nhash = 1u << kMxHashBits;
+  static const std::vector<int> doubled = [] {
+    std::vector<int> t(2 * nhash);
+    for (uint32_t h = 0; h < nhash; ++h) {
+      t[h] = static_cast<int>(
+          2.0 * decode_e4m3(dense_code_from_hash(kDenseFp8, h)));
+      t[nhash + h] = static_cast<int>(
+          2.0 * decode_e5m2(dense_code_from_hash(kDenseBf8, h)));
+    }
+    return t;
+  }();
+  auto element = [&](uint64_t h) -> int {
+    if (f == kDenseFp8) return doubled[h & (nhash - 1)];
+    if (f == kDenseBf8) return doubled[nhash + (h & (nhash - 1))];
+    return static_cast<int>(dense_int_from_hash(f, h));
+  };
+  std::vector<Acc> a(static_cast<size_t>(mn) * K), b(static_cast<size_t>(K) * mn);
+  for (int r = 0; r < mn; ++r)
+    for (int k = 0; k < K; ++k) {
+      a[r * K + k] = element(dense_a_hash(f, key_a, r, k));
+      b[k * mn + r] = element(dense_b_hash(f, key_b, k, r));
+    }
+  std::vector<Acc> sums(mn);
+  for (int row = 0; row < mn; ++row) {
+    for (int col = 0; col < mn; ++col) sums[col] = 0;
+    for (int k = 0; k < K; ++k) {
+      const Acc av = a[row * K + k];
+      const Acc* brow = &b[k * mn];
+      for (int col = 0; col < mn; ++col) sums[col] += av * brow[col];
+    }
+    for (int col = 0; col < mn; ++col) out[row * mn + col] = sums[col];
+  }
+}
+
+void dense_expected_tile(int f, uint64_t seed, long w, double* out) {
+  if (f == gpucheck::kDenseF64)
+    dense_expected_tile_as<double>(f, seed, w, out);
+  else
+    dense_expected_tile_as<float>(f, seed, w, out);
+}
+
+// The tiles in host memory, per format: tiles[f][w * mn * mn + e]. Whatever
+// the device stored (f32, i32 or f64) is held as a double, which every one of
+// them converts to exactly, NaN included; so one judge serves all formats.
+using DenseTiles = std::vector<double>[gpucheck::kDenseFormats];
+
+// Everything after the tiles are in host memory, as judge_mx.
+void judge_dense(DenseTiles& tiles, long nwaves, const Options& o,
+                 Report* rep) {
+  rep->dense_waves = nwaves;
+  std::vector<char> bad(static_cast<size_t>(gpucheck::kDenseFormats) * nwaves, 0);
+  if (o.dump_dense_wave >= 0) {
+    const int f = o.dump_dense_format;
+    const int elems = dense_tile_elems(f);
+    const double* tile = tiles[f].data() + o.dump_dense_wave * elems;
+    for (int e = 0; e < elems; ++e) {
+      const double scaled = tile[e] * gpucheck::kDenseFormatTable[f].scale;
+      // Not a finite integer a long long can hold: null in the dump (the
+      // comparison below finds the wave bad).
+      if (!(scaled >= -9e18 && scaled <= 9e18) ||
+          scaled != static_cast<double>(static_cast<long long>(scaled)))
+        rep->dense_tile.push_back(kDenseNotAnInteger);
+      else
+        rep->dense_tile.push_back(static_cast<long long>(scaled));
+    }
+  }
+  for (const Options::MxInject& m : o.dense_inject)
+    tiles[m.format][m.wave * dense_tile_elems(m.format) + m.elem] += 1.0;
+  std::vector<double> want(32 * 32);
+  bool any = false;
+  for (int f = 0; f < gpucheck::kDenseFormats; ++f) {
+    const int elems = dense_tile_elems(f);
+    const double scale = gpucheck::kDenseFormatTable[f].scale;
+    Report::DenseFormatResult& r = rep->dense_formats[f];
+    for (long w = 0; w < nwaves; ++w) {
+      dense_expected_tile(f, o.seed, w, want.data());
+      const double* tile = tiles[f].data() + w * elems;
+      char& is_bad = bad[static_cast<size_t>(f) * nwaves + w];
+      // Exact by the bounds in gpucheck_pattern.h: == is bit-exactness, and
+      // NaN compares unequal. want holds the value times the scale.
+      for (int e = 0; e < elems && !is_bad; ++e)
+        if (!(tile[e] * scale == want[e])) is_bad = 1;
+      if (is_bad) {
+        if (r.bad_waves == 0) r.first_bad_wave = w;
+        ++r.bad_waves;
+        any = true;
+      }
+    }
+  }
+  rep->dense = any ? "fail" : "pass";
+}
+
+// --cpu: the tiles come from the host product, so this exercises the
+// decoders, judge_dense and the JSON, not a device. No rate is measured.
+void run_dense_cpu(const Options& o, long nwaves, Report* rep) {
+  DenseTiles tiles;
+  std::vector<double> want(32 * 32);
+  for (int f = 0; f < gpucheck::kDenseFormats; ++f) {
+    const int elems = dense_tile_elems(f);
+    tiles[f].resize(static_cast<size_t>(nwaves) * elems);
+    for (long w = 0; w < nwaves; ++w) {
+      dense_expected_tile(f, o.seed, w, want.data());
+      for (int e = 0; e < elems; ++e)
+        tiles[f][w * elems + e] =
+            want[e] / gpucheck::kDenseFormatTable[f].scale;
+    }
+  }
+  judge_dense(tiles, nwaves, o, rep);
+}
+
+// Launches format kFmt's self-test, copies its tiles back into (*tiles)[kFmt]
+// as doubles and its where list into where[kFmt * nwaves ...]; then the next
+// format's.
+template <int kFmt>
+void run_dense_formats(long nwaves, uint64_t seed, DenseTiles* tiles,
+                       std::vector<uint32_t>* where_all) {
+  using Elem = typename DenseTypes<kFmt>::Elem;
+  const size_t n = static_cast<size_t>(nwaves) * dense_tile_elems(kFmt);
+  Elem* dev = nullptr;
+  HIP_CHECK(hipMalloc(&dev, n * sizeof(Elem)));
+  HIP_CHECK(hipMemset(dev, 0xFF, n * sizeof(Elem)));
+  WhereBuffer where(static_cast<size_t>(nwaves));
+  const unsigned int blocks = static_cast<unsigned int>((nwaves + 3) / 4);
+  hipLaunchKernelGGL(dense_selftest<kFmt>, dim3(blocks), dim3(kBlock), 0, 0,
+                     dev, where.dev, static_cast<uint32_t>(nwaves), seed);
+  HIP_CHECK(hipGetLastError());
+  std::vector<Elem> host(n);
+  HIP_CHECK(hipMemcpy(host.data(), dev, n * sizeof(Elem), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipFree(dev));
+  (*tiles)[kFmt].assign(host.begin(), host.end());
+  const std::vector<uint32_t> ran = where.fetch();
+  where_all->insert(where_all->end(), ran.begin(), ran.end());
+  if constexpr (kFmt + 1 < gpucheck::kDenseFormats)
+    run_dense_formats<kFmt + 1>(nwaves, seed, tiles, where_all);
+}
+
+// Median of five timed launches after one warm-up, as time_mx_formats. For
+// i8 the figure is 10^12 integer operations per second.
+template <int kFmt>
+void time_dense_formats(void* sink, unsigned int blocks, const Options& o,
+                        GpuTimer& timer, Report* rep) {
+  using Elem = typename DenseTypes<kFmt>::Elem;
+  constexpr gpucheck::DenseFormat fmt = gpucheck::kDenseFormatTable[kFmt];
+  const uint32_t trips = static_cast<uint32_t>((o.dense_rate_instr + 3) / 4);
+  std::vector<double> times;
+  for (int rep_i = 0; rep_i < 6; ++rep_i) {
+    timer.begin();
+    hipLaunchKernelGGL(dense_rate<kFmt>, dim3(blocks), dim3(kBlock), 0, 0,
+                       static_cast<Elem*>(sink), trips, o.seed);
+    const double s = timer.end();
+    if (rep_i > 0) times.push_back(s);
+  }
+  std::sort(times.begin(), times.end());
+  const double seconds = times[times.size() / 2];
+  const double flop =
+      2.0 * fmt.mn * fmt.mn * fmt.step_k * 4.0 * trips * (blocks * 4.0);
+  rep->dense_formats[kFmt].tflops = seconds > 0 ? flop / seconds / 1e12 : 0.0;
+  rep->dense_formats[kFmt].launch_ms = seconds * 1e3;
+  if constexpr (kFmt + 1 < gpucheck::kDenseFormats)
+    time_dense_formats<kFmt + 1>(sink, blocks, o, timer, rep);
+}
+
+void run_dense(const Options& o, long nwaves, int compute_units, Report* rep) {
+  DenseTiles tiles;
+  run_dense_formats<0>(nwaves, o.seed, &tiles, &rep->dense_where);
+  judge_dense(tiles, nwaves, o, rep);
+
+  // Two workgroups of four waves per compute unit: waves on every SIMD. The
+  // sink holds the widest element, one per lane.
+  const unsigned int blocks =
+      static_cast<unsigned int>(2 * std::max(1, compute_units));
+  void* sink = nullptr;
+  HIP_CHECK(hipMalloc(&sink, static_cast<size_t>(blocks) * kBlock * sizeof(double)));
+  GpuTimer timer;
+  timer.init();
+  time_dense_formats<0>(sink, blocks, o, timer, rep);
+  HIP_CHECK(hipFree(sink));
+  rep->dense_rate = "pass";
+  for (int f = 0; f < gpucheck::kDenseFormats; ++f)
+    if (o.min_dense_tflops[f] > 0 &&
+        rep->dense_formats[f].tflops < o.min_dense_tflops[f])
+      rep->dense_rate = "fail";
+}
+
 // -------------------------------------------------------------- LDS stage
 
 uint64_t fnv1a64(const unsigned char* p, size_t n) {
@@ -1823,6 +2326,8 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
   size_t mfma_cus = 0, mfma_simds = 0, mx_cus = 0, mx_simds = 0;
   count_where(r.mfma_where, &mfma_cus, &mfma_simds);
   count_where(r.mx_where, &mx_cus, &mx_simds);
+  size_t dense_cus = 0, dense_simds = 0;
+  count_where(r.dense_where, &dense_cus, &dense_simds);
   std::string failed;
   auto add_failed = [&](const char* name) {
     failed += failed.empty() ? "\"" : ",\"";
@@ -1834,8 +2339,10 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
   if (!strcmp(r.mfma, "fail")) add_failed("mfma");
   if (!strcmp(r.mx, "fail")) add_failed("mx");
   if (!strcmp(r.lds, "fail")) add_failed("lds");
+  if (!strcmp(r.dense, "fail")) add_failed("dense");
   if (!strcmp(r.bandwidth, "fail")) add_failed("bandwidth");
   if (!strcmp(r.mx_rate, "fail")) add_failed("mx_rate");
+  if (!strcmp(r.dense_rate, "fail")) add_failed("dense_rate");
   if (lds_coverage_required_and_partial(o, r)) add_failed("lds_coverage");
 
   printf("{\"tool\":\"gpucheck\",\"mode\":\"%s\",\"device\":\"%s\","
@@ -1932,6 +2439,39 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
          mfma_cus, mfma_simds,
          where_of(r.mfma_where, r.mfma_first_bad_wave).c_str(), mx_cus,
          mx_simds);
+  printf("\"clock_mhz\":%d,\"mx_s\":%.4f,\"dense_s\":%.4f,", r.clock_mhz,
+         r.mx_s, r.dense_s);
+  printf("\"dense\":\"%s\",\"dense_waves\":%ld,\"dense_rate\":\"%s\","
+         "\"dense_cus_covered\":%zu,\"dense_simds_covered\":%zu,"
+         "\"dense_rate_instr\":%llu,\"dense_formats\":{",
+         r.dense, r.dense_waves, r.dense_rate, dense_cus, dense_simds,
+         static_cast<unsigned long long>(o.dense_rate_instr));
+  for (int f = 0; f < gpucheck::kDenseFormats; ++f) {
+    const Report::DenseFormatResult& d = r.dense_formats[f];
+    printf("%s\"%s\":{\"bad_waves\":%ld,\"first_bad_wave\":%ld,"
+           "\"first_bad_where\":\"%s\",\"tflops\":%.3f,\"launch_ms\":%.4f}",
+           f ? "," : "", gpucheck::kDenseFormatTable[f].name, d.bad_waves,
+           d.first_bad_wave,
+           d.first_bad_wave < 0
+               ? ""
+               : where_of(r.dense_where, f * r.dense_waves + d.first_bad_wave)
+                     .c_str(),
+           d.tflops, d.launch_ms);
+  }
+  printf("},");
+  if (o.dump_dense_wave >= 0) {
+    const gpucheck::DenseFormat& fmt =
+        gpucheck::kDenseFormatTable[o.dump_dense_format];
+    printf("\"dense_tile\":{\"format\":\"%s\",\"wave\":%ld,\"rows\":%d,"
+           "\"cols\":%d,\"scale\":%d,\"values\":[",
+           fmt.name, o.dump_dense_wave, fmt.mn, fmt.mn, fmt.scale);
+    for (size_t i = 0; i < r.dense_tile.size(); ++i)
+      if (r.dense_tile[i] == kDenseNotAnInteger)
+        printf("%snull", i ? "," : "");
+      else
+        printf("%s%lld", i ? "," : "", r.dense_tile[i]);
+    printf("]},");
+  }
   printf("\"lds\":\"%s\",", r.lds);
   if (!r.lds_skip_reason.empty())
     printf("\"lds_skipped_reason\":\"%s\",",
@@ -1994,6 +2534,8 @@ int main(int argc, char** argv) {
       if (int rc = check_mx_args(o, mx_waves)) return rc;
       const long lds_groups = o.lds_groups > 0 ? o.lds_groups : 0;
       if (int rc = check_lds_args(o, lds_groups)) return rc;
+      const long dense_waves = o.dense_waves > 0 ? o.dense_waves : 0;
+      if (int rc = check_dense_args(o, dense_waves)) return rc;
       CpuBackend be(o);
       if (be.mem == nullptr) {
         fprintf(stderr, "gpucheck: cannot allocate %zu bytes\n", o.bytes);
@@ -2003,6 +2545,7 @@ int main(int argc, char** argv) {
       if (nwaves > 0) run_mfma_cpu(o, nwaves, &rep);
       if (mx_waves > 0) run_mx_cpu(o, mx_waves, &rep);
       if (lds_groups > 0) run_lds_cpu(o, lds_groups, &rep);
+      if (dense_waves > 0) run_dense_cpu(o, dense_waves, &rep);
     } else {
       int count = 0;
       HIP_CHECK(hipGetDeviceCount(&count));
@@ -2025,14 +2568,33 @@ int main(int argc, char** argv) {
       const long lds_groups =
           o.lds_groups >= 0 ? o.lds_groups : 2L * prop.multiProcessorCount;
       if (int rc = check_lds_args(o, lds_groups)) return rc;
+      long dense_waves = o.dense_waves;
+      if (dense_waves < 0) {
+        dense_waves = 4L * prop.multiProcessorCount;
+        if (o.mfma_waves > 0) dense_waves = std::min(dense_waves, o.mfma_waves);
+      }
+      if (int rc = check_dense_args(o, dense_waves)) return rc;
+      rep.clock_mhz = prop.clockRate / 1000;  // reported in kHz
       {
         GpuBackend be(o);
         run_hbm(be, o, &rep);
         run_copy(be, o, &rep);
       }
       run_mfma(o, nwaves, &rep);
-      if (mx_waves > 0) run_mx(o, mx_waves, prop.multiProcessorCount, &rep);
+      auto timed = [](double* seconds, auto&& stage) {
+        const auto s0 = std::chrono::steady_clock::now();
+        stage();
+        *seconds = CpuBackend::since(s0);
+      };
+      if (mx_waves > 0)
+        timed(&rep.mx_s, [&] {
+          run_mx(o, mx_waves, prop.multiProcessorCount, &rep);
+        });
       if (lds_groups > 0) run_lds(o, lds_groups, prop, &rep);
+      if (dense_waves > 0)
+        timed(&rep.dense_s, [&] {
+          run_dense(o, dense_waves, prop.multiProcessorCount, &rep);
+        });
     }
   } catch (const HipError& e) {
     fprintf(stderr, "gpucheck: %s\n", e.what.c_str());
@@ -2049,8 +2611,10 @@ int main(int argc, char** argv) {
   else if (!strcmp(rep.mfma, "fail")) code = 21;
   else if (!strcmp(rep.mx, "fail")) code = 24;
   else if (!strcmp(rep.lds, "fail")) code = 26;
+  else if (!strcmp(rep.dense, "fail")) code = 28;
   else if (!strcmp(rep.bandwidth, "fail")) code = 22;
   else if (!strcmp(rep.mx_rate, "fail")) code = 25;
+  else if (!strcmp(rep.dense_rate, "fail")) code = 29;
   else if (lds_coverage_required_and_partial(o, rep)) code = 27;
   const double wall_s =
       std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -179,4 +179,89 @@ GPUCHECK_HD inline uint64_t lds_key(uint64_t seed, uint32_t group,
                             (static_cast<uint64_t>(round) << 20) | group));
 }
 
+// Dense self-test: the non-scaled matrix instructions tenants issue most,
+// one format per instruction. Every wave computes one square tile D = A.B of
+// side `mn` with A [mn][k] and B [k][mn], both row-major, in k / step_k
+// chained instructions.
+//
+// Exactness, per format (a product's magnitude times K bounds the sum of the
+// magnitudes of one output's products, so every partial sum in any order and
+// grouping is bounded by it):
+//   f16, bf16x16: integers in [-15, 15]; |sum| <= 128 . 225 = 28800 < 2^24,
+//                 exact in the f32 accumulator.
+//   fp8, bf8:     multiples of 1/2 of magnitude at most 7.5 (e4m3) and 3.5
+//                 (e5m2); a product is a multiple of 1/4 and the sum at most
+//                 128 . 56.25 = 7200, 28800 quarter-units < 2^24: exact in f32.
+//   i8:           all 256 codes; |sum| <= 128 . 2^14 = 2^21, exact in i32.
+//   f32:          integers in [-511, 511]; |sum| <= 32 . 511^2 = 8355872
+//                 < 2^24. The instruction is an fmaf chain, and every product
+//                 and partial sum is an integer below 2^24: no rounding.
+//   f64:          integers in [-(2^20 - 1), 2^20 - 1]; |sum| < 32 . 2^40 = 2^45
+//                 < 2^53, exact in f64.
+// So the device result has one correct value per element and the host
+// compares with ==; NaN compares unequal. The wide f32, f64 and i8 ranges are
+// deliberate: they put bits through the whole multiplier.
+constexpr int kDenseFormats = 7;
+constexpr int kDenseF16 = 0;
+constexpr int kDenseBf16x16 = 1;
+constexpr int kDenseFp8 = 2;
+constexpr int kDenseBf8 = 3;
+constexpr int kDenseI8 = 4;
+constexpr int kDenseF32 = 5;
+constexpr int kDenseF64 = 6;
+
+struct DenseFormat {
+  const char* name;
+  int mn;      // the tile is mn x mn
+  int k;       // summed over by k / step_k instructions
+  int step_k;  // K of one instruction
+  int scale;   // a result times this is an integer
+};
+constexpr DenseFormat kDenseFormatTable[kDenseFormats] = {
+    {"f16", 32, 128, 16, 1},  {"bf16x16", 16, 128, 32, 1},
+    {"fp8", 32, 128, 16, 4},  {"bf8", 32, 128, 16, 4},
+    {"i8", 32, 128, 32, 1},   {"f32", 32, 32, 2, 1},
+    {"f64", 16, 32, 4, 1},
+};
+
+// Bit 42 keeps these keys apart from mfma_key's, mx_key's and lds_key's.
+GPUCHECK_HD inline uint64_t dense_key(uint64_t seed, uint32_t wave,
+                                      uint32_t format, uint32_t which) {
+  return mix64(seed ^ mix64((1ull << 42) | (static_cast<uint64_t>(wave) << 4) |
+                            (format << 1) | which));
+}
+
+// The hash of A[row][k] and of B[k][col] of format `f`. B[k][c] and B[c][k]
+// hash different element indices: B is not symmetric.
+GPUCHECK_HD inline uint64_t dense_a_hash(int f, uint64_t key_a, int row, int k) {
+  return mix64(key_a + static_cast<uint32_t>(row * kDenseFormatTable[f].k + k));
+}
+GPUCHECK_HD inline uint64_t dense_b_hash(int f, uint64_t key_b, int k, int col) {
+  return mix64(key_b + static_cast<uint32_t>(k * kDenseFormatTable[f].mn + col));
+}
+
+// The element of an integer-valued format from its hash.
+GPUCHECK_HD inline long long dense_int_from_hash(int f, uint64_t h) {
+  if (f == kDenseI8) return static_cast<int8_t>(h & 0xFFu);
+  if (f == kDenseF32) return static_cast<long long>(h % 1023u) - 511;
+  if (f == kDenseF64)
+    return static_cast<long long>(h % ((1ull << 21) - 1)) - ((1ll << 20) - 1);
+  return static_cast<long long>(h % 31u) - 15;
+}
+
+// The element code of fp8 (e4m3) and bf8 (e5m2) from its hash: the MX stage's.
+GPUCHECK_HD inline uint32_t dense_code_from_hash(int f, uint64_t h) {
+  return mx_code_from_hash(f == kDenseFp8 ? kMxE4M3 : kMxE5M2, h);
+}
+
+// As above but never zero (0 becomes 1, +-0 becomes +-1): the rate kernels'
+// operands.
+GPUCHECK_HD inline long long dense_nonzero_int_from_hash(int f, uint64_t h) {
+  const long long v = dense_int_from_hash(f, h);
+  return v ? v : 1;
+}
+GPUCHECK_HD inline uint32_t dense_nonzero_code_from_hash(int f, uint64_t h) {
+  return mx_nonzero_code_from_hash(f == kDenseFp8 ? kMxE4M3 : kMxE5M2, h);
+}
+
 }  // namespace gpucheck

@@ -476,7 +476,9 @@ class ProcessRuntime(Runtime):
             argv[0] = self.podworker_path()
         elif argv[0] in ("gpucheck", "amdvk-gpucheck"):
             # the GPU self-test as a pod (a Job): its exit code is the
-            # container's (0 pass, 20 HBM, 23 copy, 21 MFMA, 22 bandwidth)
+            # container's (0 pass, 20 HBM, 23 copy, 21 MFMA, 24 MX, 26 LDS,
+            # 28 dense, 22 bandwidth, 25 MX rate, 29 dense rate, 27 LDS
+            # coverage)
             from ..ops import gpucheck_binary
 
             argv[0] = gpucheck_binary()

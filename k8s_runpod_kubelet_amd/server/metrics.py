@@ -104,6 +104,11 @@ gpu_check_mx_tflops = Gauge("amdvk_gpu_check_mx_tflops",
                             "Block-scaled MX MFMA rate of the last self-test "
                             "(TFLOP/s)",
                             ["gpu", "format"], registry=registry)
+gpu_check_dense_tflops = Gauge("amdvk_gpu_check_dense_tflops",
+                               "Dense MFMA rate of the last self-test by "
+                               "format (TFLOP/s; i8: 10^12 integer "
+                               "operations per second)",
+                               ["gpu", "format"], registry=registry)
 gpu_check_lds_cus_covered = Gauge("amdvk_gpu_check_lds_cus_covered",
                                   "Compute units whose LDS the last self-test "
                                   "covered",
@@ -134,12 +139,17 @@ def observe_gpu_check(index: int, result, verdict_ok: bool) -> None:
         value = result.data.get(key)
         if isinstance(value, (int, float)):
             gauge.labels(label).set(value)
-    formats = result.data.get("mx_formats")
-    if result.data.get("mx_rate") in ("pass", "fail") and isinstance(formats, dict):
+    # Rates only of a stage that measured them (not off, not --cpu).
+    for gauge, stage in ((gpu_check_mx_tflops, "mx"),
+                         (gpu_check_dense_tflops, "dense")):
+        formats = result.data.get(f"{stage}_formats")
+        if result.data.get(f"{stage}_rate") not in ("pass", "fail") \
+                or not isinstance(formats, dict):
+            continue
         for name, got in formats.items():
             value = got.get("tflops") if isinstance(got, dict) else None
             if isinstance(value, (int, float)):
-                gpu_check_mx_tflops.labels(label, str(name)).set(value)
+                gauge.labels(label, str(name)).set(value)
     # A run without the stage (off, or an older binary) sets nothing.
     if result.data.get("lds") in ("pass", "fail"):
         covered = result.data.get("lds_cus_covered")
