@@ -59,6 +59,7 @@
 #include <algorithm>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
 #include <type_traits>
@@ -91,7 +92,7 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 constexpr int kBlock = 256;
 constexpr size_t kMaxGrid = 2048;
 constexpr uint64_t kNoBad = ~0ull;
-constexpr long long kDenseNotAnInteger = INT64_MIN;  // below every exact value
+constexpr long long kNotAnInteger = INT64_MIN;  // below every exact value
 constexpr size_t kCacheResidentBelow = 512ull << 20;
 
 // ---------------------------------------------------------------- kernels
@@ -222,6 +223,23 @@ __global__ __launch_bounds__(kBlock) void vec_copy(u32x4* __restrict__ dst,
     dst[i] = src[i];
 }
 
+// The tile a wave of a *_selftest kernel computes: four waves per workgroup.
+__device__ inline uint32_t selftest_wave() {
+  return blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+}
+
+// The C/D map of the 32x32 f32 forms: lane (r, h) stores accumulator register
+// g to out[wave][(g & 3) + 8 (g >> 2) + 4 h][r].
+__device__ inline void store_tile_32x32(float* __restrict__ out, uint32_t wave,
+                                        int r, int h, const f32x16& acc) {
+  float* tile = out + static_cast<size_t>(wave) * (32 * 32);
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
+    tile[row * 32 + r] = acc[g];
+  }
+}
+
 // Each wave computes one 32x32 tile D = A.B with K = 128 from operands
 // generated in registers, then stores it to out[wave][row][col]. Lane l
 // (r = l & 31, h = l >> 5) holds A[r][8h+j] and B[8h+j][r] of each 16-wide
@@ -230,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void vec_copy(u32x4* __restrict__ dst,
 __global__ __launch_bounds__(kBlock) void mfma_selftest(
     float* __restrict__ out, uint32_t* __restrict__ where, uint32_t nwaves,
     uint64_t seed) {
-  const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  const uint32_t wave = selftest_wave();
   // Wave-uniform: surplus waves of the last workgroup leave whole, so every
   // MFMA below runs with a full EXEC mask.
   if (wave >= nwaves) return;
@@ -256,12 +274,7 @@ __global__ __launch_bounds__(kBlock) void mfma_selftest(
         __builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0,
         0, 0);
   }
-  float* tile = out + static_cast<size_t>(wave) * (32 * 32);
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
-    tile[row * 32 + r] = acc[g];
-  }
+  store_tile_32x32(out, wave, r, h, acc);
   if (lane == 0) store_where(where, wave);
 }
 
@@ -332,7 +345,7 @@ template <int kFmt>
 __global__ __launch_bounds__(kBlock) void mx_selftest(
     float* __restrict__ out, uint32_t* __restrict__ where, uint32_t nwaves,
     uint64_t seed) {
-  const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  const uint32_t wave = selftest_wave();
   // Wave-uniform, as in mfma_selftest: EXEC is full at every MFMA.
   if (wave >= nwaves) return;
   const int lane = threadIdx.x & 63;
@@ -353,12 +366,7 @@ __global__ __launch_bounds__(kBlock) void mx_selftest(
   acc = mx_step<kFmt, 1>(acc, key_a, key_b, r, h, sa, sb);
   acc = mx_step<kFmt, 2>(acc, key_a, key_b, r, h, sa, sb);
   acc = mx_step<kFmt, 3>(acc, key_a, key_b, r, h, sa, sb);
-  float* tile = out + static_cast<size_t>(wave) * (32 * 32);
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
-    tile[row * 32 + r] = acc[g];
-  }
+  store_tile_32x32(out, wave, r, h, acc);
   if (lane == 0) store_where(where, wave);
 }
 
@@ -528,7 +536,7 @@ __global__ __launch_bounds__(kBlock) void dense_selftest(
     uint32_t* __restrict__ where, uint32_t nwaves, uint64_t seed) {
   using T = DenseTypes<kFmt>;
   constexpr int mn = T::fmt.mn, K = T::fmt.k, step_k = T::fmt.step_k;
-  const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  const uint32_t wave = selftest_wave();
   // Wave-uniform, as in mfma_selftest: EXEC is full at every MFMA.
   if (wave >= nwaves) return;
   const int lane = threadIdx.x & 63;
@@ -734,7 +742,87 @@ __global__ __launch_bounds__(kBlock) void lds_selftest(
   if ((t & 63) == 0) store_where(where, 4 * static_cast<size_t>(group) + (t >> 6));
 }
 
+// ------------------------------------------------------- tile-stage families
+//
+// The MFMA, MX and dense stages are one thing on the host: one wave per tile,
+// tiles compared exactly with a host product, a rate kernel per format. What
+// differs between them is in this table and in their kernels.
+
+enum { kMfma, kMx, kDense, kFamilies };
+constexpr int kMaxFormats = gpucheck::kDenseFormats;
+
+// The tile wave `w` must produce in format `f`, times the format's scale,
+// row-major.
+void mfma_expected_tile(int f, uint64_t seed, long w, double* out);
+void mx_expected_tile(int f, uint64_t seed, long w, double* out);
+void dense_expected_tile(int f, uint64_t seed, long w, double* out);
+
+struct Family {
+  const char* prefix;  // of its flags and JSON keys
+  int formats;
+  const char* names[kMaxFormats];  // MFMA's one format has no name
+  int elems[kMaxFormats];          // of one tile
+  int scale[kMaxFormats];          // a result times this is an integer
+  // A dumped value times the scale is printed if it is an integer of at most
+  // this magnitude.
+  double dump_bound;
+  void (*expected_tile)(int f, uint64_t seed, long w, double* out);
+  bool optional;            // --X-waves 0 skips the stage
+  int waves_per_cu;         // default waves, per compute unit
+  uint64_t rate_instr;      // default timed MFMAs per wave and launch; 0: no rate
+};
+
+Family mx_family() {
+  Family fam = {"mx", gpucheck::kMxFormats, {}, {}, {}, 1e15,
+                mx_expected_tile, true, 4, 65536};
+  for (int f = 0; f < fam.formats; ++f) {
+    fam.names[f] = gpucheck::kMxFormatTable[f].name;
+    fam.elems[f] = 32 * 32;
+    fam.scale[f] = 16;
+  }
+  return fam;
+}
+
+Family dense_family() {
+  Family fam = {"dense", gpucheck::kDenseFormats, {}, {}, {}, 9e18,
+                dense_expected_tile, true, 4, 16384};
+  for (int f = 0; f < fam.formats; ++f) {
+    const gpucheck::DenseFormat& fmt = gpucheck::kDenseFormatTable[f];
+    fam.names[f] = fmt.name;
+    fam.elems[f] = fmt.mn * fmt.mn;
+    fam.scale[f] = fmt.scale;
+  }
+  return fam;
+}
+
+const Family kFamilyTable[kFamilies] = {
+    {"mfma", 1, {nullptr}, {32 * 32}, {1}, 16777216.0, mfma_expected_tile,
+     false, 8, 0},
+    mx_family(),
+    dense_family(),
+};
+
 // ---------------------------------------------------------------- options
+
+// One changed element of the host copy of a tile.
+struct Inject {
+  int format;
+  long wave;
+  int elem;
+};
+
+// The flags of one family: --X-waves, --dump-X-tile, --inject-X,
+// --min-X-tflops and --X-rate-instr.
+struct TileOptions {
+  // -1: the family's waves_per_cu x multiProcessorCount, capped by an explicit
+  // --mfma-waves so that a small run stays small.
+  long waves = -1;
+  int dump_format = -1;
+  long dump_wave = -1;
+  std::vector<Inject> inject;
+  double min_tflops[kMaxFormats] = {};
+  uint64_t rate_instr = 0;
+};
 
 struct Options {
   bool cpu = false;
@@ -743,7 +831,6 @@ struct Options {
   uint64_t base_index = 0;
   uint64_t seed = 0x6770756368656B31ull;
   double min_copy_gbs = 0.0;
-  long mfma_waves = -1;  // -1: 8 x multiProcessorCount
   struct Flip {
     size_t offset;
     int bit;
@@ -755,31 +842,12 @@ struct Options {
   bool dump_pattern = false;
   std::vector<size_t> dump_vectors;
   int store_variant = -1;  // -1 auto, 0 plain, 1 non-temporal
-  long dump_mfma_tile = -1;
-  struct MfmaInject {
-    long wave;
-    int elem;
-  };
-  std::vector<MfmaInject> mfma_inject;
-  // MX stage. Formats are indices into gpucheck::kMxFormatTable.
-  long mx_waves = -1;  // -1: 4 x multiProcessorCount, capped by --mfma-waves
-  int dump_mx_format = -1;
-  long dump_mx_wave = -1;
-  struct MxInject {
-    int format;
-    long wave;
-    int elem;
-  };
-  std::vector<MxInject> mx_inject;
-  double min_mx_tflops[gpucheck::kMxFormats] = {0, 0, 0, 0};
-  uint64_t mx_rate_instr = 65536;  // timed MFMAs per wave and launch
-  // Dense stage. Formats are indices into gpucheck::kDenseFormatTable.
-  long dense_waves = -1;  // -1: 4 x multiProcessorCount, capped by --mfma-waves
-  int dump_dense_format = -1;
-  long dump_dense_wave = -1;
-  std::vector<MxInject> dense_inject;
-  double min_dense_tflops[gpucheck::kDenseFormats] = {0, 0, 0, 0, 0, 0, 0};
-  uint64_t dense_rate_instr = 16384;  // timed MFMAs per wave and launch
+  // MFMA, MX and dense stages. Formats are indices into the family's names.
+  TileOptions tile[kFamilies];
+  Options() {
+    for (int fam = 0; fam < kFamilies; ++fam)
+      tile[fam].rate_instr = kFamilyTable[fam].rate_instr;
+  }
   // LDS stage.
   long lds_groups = -1;  // -1: 2 x multiProcessorCount (0 under --cpu)
   uint32_t lds_rounds = 4;
@@ -796,9 +864,7 @@ struct Options {
 
 constexpr size_t kMaxFlips = 16;
 constexpr size_t kMaxDumpVectors = 16;
-constexpr size_t kMaxMfmaInject = 8;
-constexpr size_t kMaxMxInject = 8;
-constexpr size_t kMaxDenseInject = 8;
+constexpr size_t kMaxInject = 8;  // per family
 const char* const kVariantNames[2] = {"plain", "nontemporal"};
 
 bool parse_u64(const char* s, uint64_t* out, bool allow_suffix) {
@@ -898,30 +964,62 @@ bool parse_fields(const char* v, size_t n, uint64_t* out) {
   return true;
 }
 
-// "FORMAT:REST": the index of the named MX format, or -1; *rest is REST.
-int parse_mx_format(const char* v, const char** rest) {
+// "FORMAT:REST": the index of the family's named format, or -1; *rest is
+// REST. A family whose one format has no name takes all of `v` as REST.
+int parse_format(const Family& fam, const char* v, const char** rest) {
+  *rest = v;
+  if (fam.names[0] == nullptr) return 0;
   const char* colon = v ? strchr(v, ':') : nullptr;
   if (colon == nullptr) return -1;
   const std::string name(v, colon - v);
   *rest = colon + 1;
-  for (int f = 0; f < gpucheck::kMxFormats; ++f)
-    if (name == gpucheck::kMxFormatTable[f].name) return f;
+  for (int f = 0; f < fam.formats; ++f)
+    if (name == fam.names[f]) return f;
   return -1;
 }
 
-// The same for the dense formats.
-int parse_dense_format(const char* v, const char** rest) {
-  const char* colon = v ? strchr(v, ':') : nullptr;
-  if (colon == nullptr) return -1;
-  const std::string name(v, colon - v);
-  *rest = colon + 1;
-  for (int f = 0; f < gpucheck::kDenseFormats; ++f)
-    if (name == gpucheck::kDenseFormatTable[f].name) return f;
+// The five flags of every family. `next` yields the flag's value. Returns -1
+// where `a` is none of them, else 0, or 2 on a usage error.
+template <typename Next>
+int parse_tile_flag(const std::string& a, Next&& next, Options* o) {
+  for (int i = 0; i < kFamilies; ++i) {
+    const Family& fam = kFamilyTable[i];
+    TileOptions& t = o->tile[i];
+    const std::string x = fam.prefix;
+    const char* rest = nullptr;
+    uint64_t u = 0, elem = 0;
+    if (a == "--" + x + "-waves") {
+      if (!parse_u64(next(), &u, false) || (u == 0 && !fam.optional) ||
+          u > 65536)
+        return usage("bad value for", a.c_str());
+      t.waves = static_cast<long>(u);
+    } else if (a == "--dump-" + x + "-tile") {
+      const int f = parse_format(fam, next(), &rest);
+      if (f < 0 || !parse_u64(rest, &u, false) || u >= 65536)
+        return usage("bad value for", a.c_str());
+      t.dump_format = f;
+      t.dump_wave = static_cast<long>(u);
+    } else if (a == "--inject-" + x) {
+      const int f = parse_format(fam, next(), &rest);
+      if (f < 0 || !parse_pair(rest, &u, &elem) || u >= 65536 ||
+          elem >= static_cast<uint64_t>(fam.elems[f]))
+        return usage("bad value for", a.c_str());
+      if (t.inject.size() == kMaxInject) return usage("too many", a.c_str());
+      t.inject.push_back({f, static_cast<long>(u), static_cast<int>(elem)});
+    } else if (fam.rate_instr != 0 && a == "--min-" + x + "-tflops") {
+      const int f = parse_format(fam, next(), &rest);
+      if (f < 0 || !parse_double(rest, &t.min_tflops[f]))
+        return usage("bad value for", a.c_str());
+    } else if (fam.rate_instr != 0 && a == "--" + x + "-rate-instr") {
+      if (!parse_u64(next(), &u, false) || u == 0 || u > (1ull << 30))
+        return usage("bad value for", a.c_str());
+      t.rate_instr = u;
+    } else {
+      continue;
+    }
+    return 0;
+  }
   return -1;
-}
-
-int dense_tile_elems(int f) {
-  return gpucheck::kDenseFormatTable[f].mn * gpucheck::kDenseFormatTable[f].mn;
 }
 
 // Returns 0 on success, 2 on a usage error.
@@ -932,7 +1030,9 @@ int parse_args(int argc, char** argv, Options* o) {
       return (i + 1 < argc) ? argv[++i] : nullptr;
     };
     uint64_t u = 0;
-    if (a == "--cpu") {
+    if (const int rc = parse_tile_flag(a, next, o); rc >= 0) {
+      if (rc != 0) return rc;
+    } else if (a == "--cpu") {
       o->cpu = true;
     } else if (a == "--dump-pattern") {
       o->dump_pattern = true;
@@ -953,10 +1053,6 @@ int parse_args(int argc, char** argv, Options* o) {
     } else if (a == "--min-copy-gbs") {
       if (!parse_double(next(), &o->min_copy_gbs))
         return usage("bad value for", "--min-copy-gbs");
-    } else if (a == "--mfma-waves") {
-      if (!parse_u64(next(), &u, false) || u == 0 || u > 65536)
-        return usage("bad value for", "--mfma-waves");
-      o->mfma_waves = static_cast<long>(u);
     } else if (a == "--inject-flip") {
       uint64_t bit = 0;
       if (!parse_pair(next(), &u, &bit) || bit > 7)
@@ -995,78 +1091,6 @@ int parse_args(int argc, char** argv, Options* o) {
       else if (s == kVariantNames[0]) o->store_variant = 0;
       else if (s == kVariantNames[1]) o->store_variant = 1;
       else return usage("bad value for", "--store-variant");
-    } else if (a == "--dump-mfma-tile") {
-      if (!parse_u64(next(), &u, false) || u >= 65536)
-        return usage("bad value for", "--dump-mfma-tile");
-      o->dump_mfma_tile = static_cast<long>(u);
-    } else if (a == "--inject-mfma") {
-      uint64_t elem = 0;
-      if (!parse_pair(next(), &u, &elem) || u >= 65536 || elem >= 32 * 32)
-        return usage("bad value for", "--inject-mfma");
-      if (o->mfma_inject.size() == kMaxMfmaInject)
-        return usage("too many", "--inject-mfma");
-      o->mfma_inject.push_back({static_cast<long>(u), static_cast<int>(elem)});
-    } else if (a == "--mx-waves") {
-      if (!parse_u64(next(), &u, false) || u > 65536)
-        return usage("bad value for", "--mx-waves");
-      o->mx_waves = static_cast<long>(u);
-    } else if (a == "--dump-mx-tile") {
-      const char* rest = nullptr;
-      const int f = parse_mx_format(next(), &rest);
-      if (f < 0 || !parse_u64(rest, &u, false) || u >= 65536)
-        return usage("bad value for", "--dump-mx-tile");
-      o->dump_mx_format = f;
-      o->dump_mx_wave = static_cast<long>(u);
-    } else if (a == "--inject-mx") {
-      const char* rest = nullptr;
-      uint64_t elem = 0;
-      const int f = parse_mx_format(next(), &rest);
-      if (f < 0 || !parse_pair(rest, &u, &elem) || u >= 65536 ||
-          elem >= 32 * 32)
-        return usage("bad value for", "--inject-mx");
-      if (o->mx_inject.size() == kMaxMxInject)
-        return usage("too many", "--inject-mx");
-      o->mx_inject.push_back({f, static_cast<long>(u), static_cast<int>(elem)});
-    } else if (a == "--min-mx-tflops") {
-      const char* rest = nullptr;
-      const int f = parse_mx_format(next(), &rest);
-      if (f < 0 || !parse_double(rest, &o->min_mx_tflops[f]))
-        return usage("bad value for", "--min-mx-tflops");
-    } else if (a == "--mx-rate-instr") {
-      if (!parse_u64(next(), &u, false) || u == 0 || u > (1ull << 30))
-        return usage("bad value for", "--mx-rate-instr");
-      o->mx_rate_instr = u;
-    } else if (a == "--dense-waves") {
-      if (!parse_u64(next(), &u, false) || u > 65536)
-        return usage("bad value for", "--dense-waves");
-      o->dense_waves = static_cast<long>(u);
-    } else if (a == "--dump-dense-tile") {
-      const char* rest = nullptr;
-      const int f = parse_dense_format(next(), &rest);
-      if (f < 0 || !parse_u64(rest, &u, false) || u >= 65536)
-        return usage("bad value for", "--dump-dense-tile");
-      o->dump_dense_format = f;
-      o->dump_dense_wave = static_cast<long>(u);
-    } else if (a == "--inject-dense") {
-      const char* rest = nullptr;
-      uint64_t elem = 0;
-      const int f = parse_dense_format(next(), &rest);
-      if (f < 0 || !parse_pair(rest, &u, &elem) || u >= 65536 ||
-          elem >= static_cast<uint64_t>(dense_tile_elems(f)))
-        return usage("bad value for", "--inject-dense");
-      if (o->dense_inject.size() == kMaxDenseInject)
-        return usage("too many", "--inject-dense");
-      o->dense_inject.push_back(
-          {f, static_cast<long>(u), static_cast<int>(elem)});
-    } else if (a == "--min-dense-tflops") {
-      const char* rest = nullptr;
-      const int f = parse_dense_format(next(), &rest);
-      if (f < 0 || !parse_double(rest, &o->min_dense_tflops[f]))
-        return usage("bad value for", "--min-dense-tflops");
-    } else if (a == "--dense-rate-instr") {
-      if (!parse_u64(next(), &u, false) || u == 0 || u > (1ull << 30))
-        return usage("bad value for", "--dense-rate-instr");
-      o->dense_rate_instr = u;
     } else if (a == "--lds-groups") {
       if (!parse_u64(next(), &u, false) || u > 65536)
         return usage("bad value for", "--lds-groups");
@@ -1129,36 +1153,20 @@ int parse_args(int argc, char** argv, Options* o) {
   return 0;
 }
 
-// The MFMA flags name waves, and how many waves run is known only once the
+int wave_outside_run(const std::string& flag) {
+  return usage((flag + " wave is outside the run").c_str(), nullptr);
+}
+
+// A family's flags name waves, and how many waves run is known only once the
 // device is. 0 waves: the stage does not run.
-int check_mfma_args(const Options& o, long nwaves) {
-  if (o.dump_mfma_tile >= nwaves)
-    return usage("--dump-mfma-tile wave is outside the run", nullptr);
-  for (const Options::MfmaInject& m : o.mfma_inject)
-    if (m.wave >= nwaves)
-      return usage("--inject-mfma wave is outside the run", nullptr);
+int check_tile_args(const Family& fam, const TileOptions& t, long nwaves) {
+  const std::string x = fam.prefix;
+  if (t.dump_wave >= nwaves) return wave_outside_run("--dump-" + x + "-tile");
+  for (const Inject& m : t.inject)
+    if (m.wave >= nwaves) return wave_outside_run("--inject-" + x);
   return 0;
 }
 
-// The same for the MX flags.
-int check_mx_args(const Options& o, long nwaves) {
-  if (o.dump_mx_wave >= nwaves)
-    return usage("--dump-mx-tile wave is outside the run", nullptr);
-  for (const Options::MxInject& m : o.mx_inject)
-    if (m.wave >= nwaves)
-      return usage("--inject-mx wave is outside the run", nullptr);
-  return 0;
-}
-
-// The same for the dense flags.
-int check_dense_args(const Options& o, long nwaves) {
-  if (o.dump_dense_wave >= nwaves)
-    return usage("--dump-dense-tile wave is outside the run", nullptr);
-  for (const Options::MxInject& m : o.dense_inject)
-    if (m.wave >= nwaves)
-      return usage("--inject-dense wave is outside the run", nullptr);
-  return 0;
-}
 
 // The same for the LDS flags: they name workgroups and rounds of the run.
 int check_lds_args(const Options& o, long groups) {
@@ -1199,41 +1207,26 @@ struct Report {
   bool have_copy_first_bad = false;
   uint64_t copy_first_bad_offset = 0;  // within the whole region
   Vec16 copy_first_bad_xor{0, 0};
-  // MFMA
-  const char* mfma = "skipped";
-  long mfma_waves = 0, mfma_bad_waves = 0, mfma_first_bad_wave = -1;
-  bool mfma_tile_valid = false;
-  std::vector<int> mfma_tile;
-  // MX
-  const char* mx = "skipped";
-  const char* mx_rate = "skipped";
-  long mx_waves = 0;
-  struct MxFormatResult {
-    long bad_waves = 0, first_bad_wave = -1;
-    double tflops = 0;
+  // MFMA, MX and dense
+  struct TileResult {
+    const char* verdict = "skipped";
+    const char* rate = "skipped";
+    long waves = 0;
+    struct Format {
+      long bad_waves = 0, first_bad_wave = -1;
+      double tflops = 0, launch_ms = 0;
+    };
+    Format formats[kMaxFormats];
+    // The dumped tile, values times the format's scale; kNotAnInteger where
+    // that is none within the family's bound.
+    std::vector<long long> dump;
+    // Where the waves ran: [cu key, simd] per format and wave, format-major.
+    // Empty under --cpu.
+    std::vector<uint32_t> where;
+    double seconds = 0;  // wall time of the stage, host product included
   };
-  MxFormatResult mx_formats[gpucheck::kMxFormats];
-  bool mx_tile_valid = false;
-  std::vector<long> mx_tile;  // values times 16
-  // Where the MFMA and MX waves ran: [cu key, simd] per wave (MX: per format
-  // and wave). Empty under --cpu.
-  std::vector<uint32_t> mfma_where, mx_where;
-  double mx_s = 0;  // wall time of the MX stage, host product included
-  // Dense
+  TileResult tile[kFamilies];
   int clock_mhz = 0;  // the device's reported clock; 0 under --cpu
-  const char* dense = "skipped";
-  const char* dense_rate = "skipped";
-  long dense_waves = 0;
-  struct DenseFormatResult {
-    long bad_waves = 0, first_bad_wave = -1;
-    double tflops = 0, launch_ms = 0;
-  };
-  DenseFormatResult dense_formats[gpucheck::kDenseFormats];
-  // Values times the format's scale; kDenseNotAnInteger where that is none.
-  std::vector<long long> dense_tile;
-  // [cu key, simd] per format and wave, format-major. Empty under --cpu.
-  std::vector<uint32_t> dense_where;
-  double dense_s = 0;  // wall time of the dense stage
   // LDS
   const char* lds = "skipped";
   std::string lds_skip_reason;
@@ -1347,6 +1340,20 @@ struct GpuTimer {
     if (stop) (void)hipEventDestroy(stop);
   }
 };
+
+// The median of five timed launches after one that warms up.
+template <typename Launch>
+double median_launch_seconds(GpuTimer& timer, Launch&& launch) {
+  std::vector<double> times;
+  for (int rep_i = 0; rep_i < 6; ++rep_i) {
+    timer.begin();
+    launch();
+    const double s = timer.end();
+    if (rep_i > 0) times.push_back(s);
+  }
+  std::sort(times.begin(), times.end());
+  return times[times.size() / 2];
+}
 
 struct GpuBackend : Backend {
   const Options& o;
@@ -1480,15 +1487,10 @@ void run_copy(GpuBackend& be, const Options& o, Report* rep) {
   const size_t half = be.nvec / 2;
   if (half == 0) return;  // a one-vector region has nothing to copy
   const dim3 grid(grid_for(half)), block(kBlock);
-  std::vector<double> times;
-  for (int rep_i = 0; rep_i < 6; ++rep_i) {
-    be.timer.begin();
+  const double seconds = median_launch_seconds(be.timer, [&] {
     hipLaunchKernelGGL(vec_copy, grid, block, 0, 0, be.mem + half, be.mem, half);
-    const double s = be.timer.end();
-    if (rep_i > 0) times.push_back(s);  // the first repetition warms up
-  }
-  std::sort(times.begin(), times.end());
-  rep->copy_gbs = gbs(2.0 * 16.0 * static_cast<double>(half), times[times.size() / 2]);
+  });
+  rep->copy_gbs = gbs(2.0 * 16.0 * static_cast<double>(half), seconds);
   rep->bandwidth =
       (o.min_copy_gbs > 0 && rep->copy_gbs < o.min_copy_gbs) ? "fail" : "pass";
 
@@ -1510,8 +1512,9 @@ void run_copy(GpuBackend& be, const Options& o, Report* rep) {
   }
 }
 
-// The 32x32 tile wave `w` must produce, as integers, row-major.
-void mfma_expected_tile(uint64_t seed, long w, int* out) {
+// The 32x32 tile wave `w` must produce, row-major: integers of magnitude
+// <= 1152.
+void mfma_expected_tile(int, uint64_t seed, long w, double* out) {
   using gpucheck::kMfmaK;
   std::vector<int> a(32 * kMfmaK), bt(32 * kMfmaK);
   const uint64_t key_a = gpucheck::mfma_key(seed, static_cast<uint32_t>(w), 0);
@@ -1530,71 +1533,74 @@ void mfma_expected_tile(uint64_t seed, long w, int* out) {
     }
 }
 
-// bad[w] != 0 where tile w of `host` differs from the expected product.
-std::vector<char> mfma_compare(const std::vector<float>& host, long nwaves,
-                               uint64_t seed) {
-  std::vector<char> bad(static_cast<size_t>(nwaves), 0);
-  std::vector<int> want(32 * 32);
-  for (long w = 0; w < nwaves; ++w) {
-    mfma_expected_tile(seed, w, want.data());
-    const float* tile = host.data() + static_cast<size_t>(w) * 32 * 32;
-    // Every value is an integer of magnitude <= 1152, so equality of the
-    // floats is bit-exactness (NaN compares unequal and is caught).
-    for (int e = 0; e < 32 * 32; ++e)
-      if (!(tile[e] == static_cast<float>(want[e]))) {
-        bad[w] = 1;
-        break;
-      }
-  }
-  return bad;
-}
+// A family's tiles in host memory, per format: tiles[f][w * elems + e].
+// Whatever the device stored (f32, i32 or f64) is held as a double, which
+// every one of them converts to exactly, NaN included; so one judge serves
+// all formats.
+using Tiles = std::vector<double>[kMaxFormats];
 
 // Everything after the tiles are in host memory: the dump, the injections,
 // the comparison and the verdict.
-void judge_mfma(std::vector<float>& host, long nwaves, const Options& o,
-                Report* rep) {
-  rep->mfma_waves = nwaves;
-  bool dump_bad = false;
-  if (o.dump_mfma_tile >= 0) {
-    const float* tile =
-        host.data() + static_cast<size_t>(o.dump_mfma_tile) * 32 * 32;
-    rep->mfma_tile_valid = true;
-    for (int e = 0; e < 32 * 32; ++e) {
-      const float v = tile[e];
-      // Not a finite integer an int can hold: no dump, and the wave is bad.
-      if (!(v >= -16777216.0f && v <= 16777216.0f) ||
-          v != static_cast<float>(static_cast<int>(v))) {
-        rep->mfma_tile_valid = false;
-        dump_bad = true;
-        break;
-      }
-      rep->mfma_tile.push_back(static_cast<int>(v));
+void judge_tiles(const Family& fam, Tiles& tiles, long nwaves,
+                 const TileOptions& t, uint64_t seed, Report::TileResult* r) {
+  r->waves = nwaves;
+  if (t.dump_wave >= 0) {
+    const int f = t.dump_format;
+    const double* tile = tiles[f].data() + t.dump_wave * fam.elems[f];
+    for (int e = 0; e < fam.elems[f]; ++e) {
+      const double scaled = tile[e] * fam.scale[f];
+      // Not a finite integer within the bound: no value in the dump (the
+      // comparison below finds the wave bad: every expected value is an
+      // integer within the bound).
+      const bool integer =
+          scaled >= -fam.dump_bound && scaled <= fam.dump_bound &&
+          scaled == static_cast<double>(static_cast<long long>(scaled));
+      r->dump.push_back(integer ? static_cast<long long>(scaled)
+                                : kNotAnInteger);
     }
   }
-  for (const Options::MfmaInject& m : o.mfma_inject)
-    host[static_cast<size_t>(m.wave) * 32 * 32 + m.elem] += 1.0f;
-  std::vector<char> bad = mfma_compare(host, nwaves, o.seed);
-  if (dump_bad) bad[o.dump_mfma_tile] = 1;
-  for (long w = 0; w < nwaves; ++w)
-    if (bad[w]) {
-      if (rep->mfma_bad_waves == 0) rep->mfma_first_bad_wave = w;
-      ++rep->mfma_bad_waves;
+  for (const Inject& m : t.inject)
+    tiles[m.format][m.wave * fam.elems[m.format] + m.elem] += 1.0;
+  std::vector<double> want(32 * 32);
+  bool any = false;
+  for (int f = 0; f < fam.formats; ++f) {
+    Report::TileResult::Format& fr = r->formats[f];
+    for (long w = 0; w < nwaves; ++w) {
+      fam.expected_tile(f, seed, w, want.data());
+      const double* tile = tiles[f].data() + w * fam.elems[f];
+      // Exact by the bounds in gpucheck_pattern.h (MFMA: integers of magnitude
+      // <= 1152): == is bit-exactness, and NaN compares unequal. want holds
+      // the value times the scale.
+      bool bad = false;
+      for (int e = 0; e < fam.elems[f] && !bad; ++e)
+        bad = !(tile[e] * fam.scale[f] == want[e]);
+      if (bad) {
+        if (fr.bad_waves == 0) fr.first_bad_wave = w;
+        ++fr.bad_waves;
+        any = true;
+      }
     }
-  rep->mfma = rep->mfma_bad_waves ? "fail" : "pass";
+  }
+  r->verdict = any ? "fail" : "pass";
 }
 
-// --cpu: the tiles come from the host integer matmul, so this exercises
-// judge_mfma and the JSON, not a device.
-void run_mfma_cpu(const Options& o, long nwaves, Report* rep) {
-  std::vector<float> host(static_cast<size_t>(nwaves) * 32 * 32);
-  std::vector<int> tile(32 * 32);
-  for (long w = 0; w < nwaves; ++w) {
-    mfma_expected_tile(o.seed, w, tile.data());
-    for (int e = 0; e < 32 * 32; ++e)
-      host[static_cast<size_t>(w) * 32 * 32 + e] = static_cast<float>(tile[e]);
+// --cpu: the tiles come from the host product, so this exercises the
+// decoders, judge_tiles and the JSON, not a device. No rate is measured.
+void run_tiles_cpu(const Family& fam, long nwaves, const TileOptions& t,
+                   uint64_t seed, Report::TileResult* r) {
+  Tiles tiles;
+  std::vector<double> want(32 * 32);
+  for (int f = 0; f < fam.formats; ++f) {
+    tiles[f].resize(static_cast<size_t>(nwaves) * fam.elems[f]);
+    for (long w = 0; w < nwaves; ++w) {
+      fam.expected_tile(f, seed, w, want.data());
+      for (int e = 0; e < fam.elems[f]; ++e)
+        tiles[f][w * fam.elems[f] + e] = want[e] / fam.scale[f];
+    }
   }
-  judge_mfma(host, nwaves, o, rep);
+  judge_tiles(fam, tiles, nwaves, t, seed, r);
 }
+
 
 // [cu key, simd] per wave on the device, preset to all ones.
 struct WhereBuffer {
@@ -1633,22 +1639,154 @@ std::string where_of(const std::vector<uint32_t>& where, long w) {
   return where_name(where[2 * w]);
 }
 
-void run_mfma(const Options& o, long nwaves, Report* rep) {
-  const size_t nfloat = static_cast<size_t>(nwaves) * 32 * 32;
-  float* dev = nullptr;
-  HIP_CHECK(hipMalloc(&dev, nfloat * sizeof(float)));
-  HIP_CHECK(hipMemset(dev, 0xFF, nfloat * sizeof(float)));
+// One format's device round trip: `launch(blocks, tiles, where)` starts its
+// self-test, one wave per tile of `elems` values of type Elem. The tiles come
+// back into *tiles as doubles and the where list is appended to *where_all.
+template <typename Elem, typename Launch>
+void fetch_tiles(long nwaves, int elems, Launch&& launch,
+                 std::vector<double>* tiles, std::vector<uint32_t>* where_all) {
+  const size_t n = static_cast<size_t>(nwaves) * elems;
+  Elem* dev = nullptr;
+  HIP_CHECK(hipMalloc(&dev, n * sizeof(Elem)));
+  HIP_CHECK(hipMemset(dev, 0xFF, n * sizeof(Elem)));
   WhereBuffer where(static_cast<size_t>(nwaves));
-  const unsigned int blocks = static_cast<unsigned int>((nwaves + 3) / 4);
-  hipLaunchKernelGGL(mfma_selftest, dim3(blocks), dim3(kBlock), 0, 0, dev,
-                     where.dev, static_cast<uint32_t>(nwaves), o.seed);
+  launch(static_cast<unsigned int>((nwaves + 3) / 4), dev, where.dev);
   HIP_CHECK(hipGetLastError());
-  std::vector<float> host(nfloat);
-  HIP_CHECK(hipMemcpy(host.data(), dev, nfloat * sizeof(float),
-                      hipMemcpyDeviceToHost));
+  const std::unique_ptr<Elem[]> host(new Elem[n]);  // not zeroed first
+  HIP_CHECK(hipMemcpy(host.get(), dev, n * sizeof(Elem), hipMemcpyDeviceToHost));
   HIP_CHECK(hipFree(dev));
-  rep->mfma_where = where.fetch();
-  judge_mfma(host, nwaves, o, rep);
+  tiles->assign(host.get(), host.get() + n);
+  const std::vector<uint32_t> ran = where.fetch();
+  where_all->insert(where_all->end(), ran.begin(), ran.end());
+}
+
+// call(std::integral_constant<int, 0>{}) ... call(<int, kCount - 1>{}), in
+// order: the format index is a template argument of the kernels.
+template <typename Call, int... kIndex>
+void for_each_index(std::integer_sequence<int, kIndex...>, Call&& call) {
+  (call(std::integral_constant<int, kIndex>{}), ...);
+}
+template <int kCount, typename Call>
+void for_each_format(Call&& call) {
+  for_each_index(std::make_integer_sequence<int, kCount>{}, call);
+}
+
+// The rate kernels of one family: two workgroups of four waves per compute
+// unit put waves on every SIMD. The sink holds the widest element, one per
+// lane.
+struct RateRun {
+  unsigned int blocks;
+  uint32_t trips;
+  void* sink = nullptr;
+  GpuTimer timer;
+  RateRun(const TileOptions& t, int compute_units)
+      : blocks(static_cast<unsigned int>(2 * std::max(1, compute_units))),
+        trips(static_cast<uint32_t>((t.rate_instr + 3) / 4)) {
+    HIP_CHECK(hipMalloc(&sink, static_cast<size_t>(blocks) * kBlock * sizeof(double)));
+    timer.init();
+  }
+  ~RateRun() {
+    if (sink) (void)hipFree(sink);
+  }
+  // `launch` issues 4 * trips MFMAs of `flop_each` per wave. For i8 the
+  // figure is 10^12 integer operations per second.
+  template <typename Launch>
+  void time(double flop_each, Launch&& launch, Report::TileResult::Format* fr) {
+    const double seconds = median_launch_seconds(timer, launch);
+    const double flop = flop_each * 4.0 * trips * (blocks * 4.0);
+    fr->tflops = seconds > 0 ? flop / seconds / 1e12 : 0.0;
+    fr->launch_ms = seconds * 1e3;
+  }
+};
+
+// Holds every format's measured rate to its floor, where one is set.
+void check_rate_floors(const Family& fam, const TileOptions& t,
+                       Report::TileResult* r) {
+  r->rate = "pass";
+  for (int f = 0; f < fam.formats; ++f)
+    if (t.min_tflops[f] > 0 && r->formats[f].tflops < t.min_tflops[f])
+      r->rate = "fail";
+}
+
+// A family's kernels: Elem<kFmt> is what a lane of format kFmt stores per
+// result, selftest<kFmt>() and rate<kFmt>() are its kernels, and flop_each(f)
+// is the operations of one of its MFMAs. MFMA has no rate kernel.
+struct MfmaKernels {
+  static constexpr int kFamily = kMfma, kFormats = 1;
+  static constexpr bool kRated = false;
+  template <int>
+  using Elem = float;
+  template <int>
+  static constexpr auto selftest() { return mfma_selftest; }
+};
+
+struct MxKernels {
+  static constexpr int kFamily = kMx, kFormats = gpucheck::kMxFormats;
+  static constexpr bool kRated = true;
+  template <int>
+  using Elem = float;
+  template <int kFmt>
+  static constexpr auto selftest() { return mx_selftest<kFmt>; }
+  template <int kFmt>
+  static constexpr auto rate() { return mx_rate<kFmt>; }
+  static double flop_each(int) { return 2.0 * 32 * 32 * 64; }
+};
+
+struct DenseKernels {
+  static constexpr int kFamily = kDense, kFormats = gpucheck::kDenseFormats;
+  static constexpr bool kRated = true;
+  template <int kFmt>
+  using Elem = typename DenseTypes<kFmt>::Elem;
+  template <int kFmt>
+  static constexpr auto selftest() { return dense_selftest<kFmt>; }
+  template <int kFmt>
+  static constexpr auto rate() { return dense_rate<kFmt>; }
+  static double flop_each(int f) {
+    const gpucheck::DenseFormat& fmt = gpucheck::kDenseFormatTable[f];
+    return 2.0 * fmt.mn * fmt.mn * fmt.step_k;
+  }
+};
+
+// One family's stage on the device: every format's tiles, judged, then every
+// format's rate, held to its floor.
+template <typename Kernels>
+void run_tiles(const Options& o, long nwaves, int compute_units, Report* rep) {
+  const auto s0 = std::chrono::steady_clock::now();
+  const Family& fam = kFamilyTable[Kernels::kFamily];
+  const TileOptions& t = o.tile[Kernels::kFamily];
+  Report::TileResult& r = rep->tile[Kernels::kFamily];
+  Tiles tiles;
+  for_each_format<Kernels::kFormats>([&](auto format) {
+    constexpr int kFmt = decltype(format)::value;
+    using Elem = typename Kernels::template Elem<kFmt>;
+    fetch_tiles<Elem>(
+        nwaves, fam.elems[kFmt],
+        [&](unsigned int blocks, Elem* dev, uint32_t* where) {
+          const auto kernel = Kernels::template selftest<kFmt>();
+          hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, 0, dev,
+                             where, static_cast<uint32_t>(nwaves), o.seed);
+        },
+        &tiles[kFmt], &r.where);
+  });
+  judge_tiles(fam, tiles, nwaves, t, o.seed, &r);
+  if constexpr (Kernels::kRated) {
+    RateRun run(t, compute_units);
+    for_each_format<Kernels::kFormats>([&](auto format) {
+      constexpr int kFmt = decltype(format)::value;
+      using Elem = typename Kernels::template Elem<kFmt>;
+      static_assert(sizeof(Elem) <= sizeof(double));
+      run.time(
+          Kernels::flop_each(kFmt),
+          [&] {
+            const auto kernel = Kernels::template rate<kFmt>();
+            hipLaunchKernelGGL(kernel, dim3(run.blocks), dim3(kBlock), 0, 0,
+                               static_cast<Elem*>(run.sink), run.trips, o.seed);
+          },
+          &r.formats[kFmt]);
+    });
+    check_rate_floors(fam, t, &r);
+  }
+  r.seconds = CpuBackend::since(s0);
 }
 
 // Decoders of the MX element and scale codes, from the OCP formulas: sign,
@@ -1687,7 +1825,7 @@ double decode_e8m0(uint32_t code) {
 // times 4 (exact: an element is a multiple of 1/2 and a scale at least 1/2)
 // and every sum is an integer below 2^24, so the float arithmetic is exact;
 // the loop order keeps the inner loop free of a reduction.
-void mx_expected_tile(int f, uint64_t seed, long w, float* out) {
+void mx_expected_tile(int f, uint64_t seed, long w, double* out) {
   using gpucheck::kMxBlock;
   using gpucheck::kMxK;
   const gpucheck::MxFormat& fmt = gpucheck::kMxFormatTable[f];
@@ -1714,7 +1852,8 @@ void mx_expected_tile(int f, uint64_t seed, long w, float* out) {
   const double* dec_a = values_of(fmt.a);
   const double* dec_b = values_of(fmt.b);
   const double* dec_scale = &table[3 * nhash];
-  std::vector<float> a(32 * kMxK), b(kMxK * 32);
+  // Kept across the thousands of calls: every element is written below.
+  static std::vector<float> a(32 * kMxK), b(kMxK * 32);
   for (int r = 0; r < 32; ++r)
     for (int blk = 0; blk < kMxK / kMxBlock; ++blk) {
       const double sa = dec_scale[gpucheck::mx_scale_byte(key_a, r, blk)];
@@ -1727,157 +1866,14 @@ void mx_expected_tile(int f, uint64_t seed, long w, float* out) {
       }
     }
   for (int row = 0; row < 32; ++row) {
-    float* sums = out + row * 32;
-    for (int col = 0; col < 32; ++col) sums[col] = 0.0f;
+    float sums[32] = {};
     for (int k = 0; k < kMxK; ++k) {
       const float av = a[row * kMxK + k];
       const float* brow = &b[k * 32];
       for (int col = 0; col < 32; ++col) sums[col] += av * brow[col];
     }
+    for (int col = 0; col < 32; ++col) out[row * 32 + col] = sums[col];
   }
-}
-
-// `host` holds the tiles format-major: host[(f * nwaves + w) * 1024 + e].
-float* mx_tile_at(std::vector<float>& host, long nwaves, int f, long w) {
-  return host.data() + (static_cast<size_t>(f) * nwaves + w) * (32 * 32);
-}
-
-// bad[f * nwaves + w] != 0 where that tile differs from the expected product.
-std::vector<char> mx_compare(std::vector<float>& host, long nwaves,
-                             uint64_t seed) {
-  std::vector<char> bad(static_cast<size_t>(gpucheck::kMxFormats) * nwaves, 0);
-  std::vector<float> want(32 * 32);
-  for (int f = 0; f < gpucheck::kMxFormats; ++f)
-    for (long w = 0; w < nwaves; ++w) {
-      mx_expected_tile(f, seed, w, want.data());
-      const float* tile = mx_tile_at(host, nwaves, f, w);
-      // Exact by the bound in gpucheck_pattern.h: == is bit-exactness, and
-      // NaN compares unequal. want holds the value times 16.
-      for (int e = 0; e < 32 * 32; ++e)
-        if (!(tile[e] * 16.0f == want[e])) {
-          bad[static_cast<size_t>(f) * nwaves + w] = 1;
-          break;
-        }
-    }
-  return bad;
-}
-
-// Everything after the tiles are in host memory, as judge_mfma.
-void judge_mx(std::vector<float>& host, long nwaves, const Options& o,
-              Report* rep) {
-  rep->mx_waves = nwaves;
-  bool dump_bad = false;
-  if (o.dump_mx_wave >= 0) {
-    const float* tile = mx_tile_at(host, nwaves, o.dump_mx_format, o.dump_mx_wave);
-    rep->mx_tile_valid = true;
-    for (int e = 0; e < 32 * 32; ++e) {
-      const float v16 = tile[e] * 16.0f;
-      // Not a finite multiple of 1/16 a long can hold: no dump, a bad wave.
-      if (!(v16 >= -1e15f && v16 <= 1e15f) ||
-          v16 != static_cast<float>(static_cast<long>(v16))) {
-        rep->mx_tile_valid = false;
-        rep->mx_tile.clear();
-        dump_bad = true;
-        break;
-      }
-      rep->mx_tile.push_back(static_cast<long>(v16));
-    }
-  }
-  for (const Options::MxInject& m : o.mx_inject)
-    mx_tile_at(host, nwaves, m.format, m.wave)[m.elem] += 1.0f;
-  std::vector<char> bad = mx_compare(host, nwaves, o.seed);
-  if (dump_bad)
-    bad[static_cast<size_t>(o.dump_mx_format) * nwaves + o.dump_mx_wave] = 1;
-  bool any = false;
-  for (int f = 0; f < gpucheck::kMxFormats; ++f) {
-    Report::MxFormatResult& r = rep->mx_formats[f];
-    for (long w = 0; w < nwaves; ++w)
-      if (bad[static_cast<size_t>(f) * nwaves + w]) {
-        if (r.bad_waves == 0) r.first_bad_wave = w;
-        ++r.bad_waves;
-        any = true;
-      }
-  }
-  rep->mx = any ? "fail" : "pass";
-}
-
-// --cpu: the tiles come from the host product, so this exercises the
-// decoders, judge_mx and the JSON, not a device. No rate is measured.
-void run_mx_cpu(const Options& o, long nwaves, Report* rep) {
-  std::vector<float> host(static_cast<size_t>(gpucheck::kMxFormats) * nwaves *
-                          32 * 32);
-  for (int f = 0; f < gpucheck::kMxFormats; ++f)
-    for (long w = 0; w < nwaves; ++w) {
-      float* tile = mx_tile_at(host, nwaves, f, w);
-      mx_expected_tile(f, o.seed, w, tile);
-      for (int e = 0; e < 32 * 32; ++e) tile[e] /= 16.0f;
-    }
-  judge_mx(host, nwaves, o, rep);
-}
-
-template <int kFmt>
-void launch_mx_formats(float* dev, uint32_t* where, long nwaves, uint64_t seed) {
-  const unsigned int blocks = static_cast<unsigned int>((nwaves + 3) / 4);
-  hipLaunchKernelGGL(mx_selftest<kFmt>, dim3(blocks), dim3(kBlock), 0, 0,
-                     dev + static_cast<size_t>(kFmt) * nwaves * 32 * 32,
-                     where + static_cast<size_t>(kFmt) * nwaves * 2,
-                     static_cast<uint32_t>(nwaves), seed);
-  if constexpr (kFmt + 1 < gpucheck::kMxFormats)
-    launch_mx_formats<kFmt + 1>(dev, where, nwaves, seed);
-}
-
-// Median of five timed launches after one warm-up, as the copy stage; two
-// workgroups of four waves per compute unit put waves on every SIMD.
-template <int kFmt>
-void time_mx_formats(float* sink, unsigned int blocks, const Options& o,
-                     GpuTimer& timer, Report* rep) {
-  const uint32_t trips = static_cast<uint32_t>((o.mx_rate_instr + 3) / 4);
-  std::vector<double> times;
-  for (int rep_i = 0; rep_i < 6; ++rep_i) {
-    timer.begin();
-    hipLaunchKernelGGL(mx_rate<kFmt>, dim3(blocks), dim3(kBlock), 0, 0, sink,
-                       trips, o.seed);
-    const double s = timer.end();
-    if (rep_i > 0) times.push_back(s);
-  }
-  std::sort(times.begin(), times.end());
-  const double seconds = times[times.size() / 2];
-  const double flop = 2.0 * 32 * 32 * 64 * 4.0 * trips * (blocks * 4.0);
-  rep->mx_formats[kFmt].tflops = seconds > 0 ? flop / seconds / 1e12 : 0.0;
-  if constexpr (kFmt + 1 < gpucheck::kMxFormats)
-    time_mx_formats<kFmt + 1>(sink, blocks, o, timer, rep);
-}
-
-void run_mx(const Options& o, long nwaves, int compute_units, Report* rep) {
-  const size_t nfloat =
-      static_cast<size_t>(gpucheck::kMxFormats) * nwaves * 32 * 32;
-  float* dev = nullptr;
-  HIP_CHECK(hipMalloc(&dev, nfloat * sizeof(float)));
-  HIP_CHECK(hipMemset(dev, 0xFF, nfloat * sizeof(float)));
-  // Format-major like the tiles: where[2 * (f * nwaves + w)].
-  WhereBuffer where(static_cast<size_t>(gpucheck::kMxFormats) * nwaves);
-  launch_mx_formats<0>(dev, where.dev, nwaves, o.seed);
-  HIP_CHECK(hipGetLastError());
-  std::vector<float> host(nfloat);
-  HIP_CHECK(hipMemcpy(host.data(), dev, nfloat * sizeof(float),
-                      hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(dev));
-  rep->mx_where = where.fetch();
-  judge_mx(host, nwaves, o, rep);
-
-  const unsigned int blocks =
-      static_cast<unsigned int>(2 * std::max(1, compute_units));
-  float* sink = nullptr;
-  HIP_CHECK(hipMalloc(&sink, static_cast<size_t>(blocks) * kBlock * sizeof(float)));
-  GpuTimer timer;
-  timer.init();
-  time_mx_formats<0>(sink, blocks, o, timer, rep);
-  HIP_CHECK(hipFree(sink));
-  rep->mx_rate = "pass";
-  for (int f = 0; f < gpucheck::kMxFormats; ++f)
-    if (o.min_mx_tflops[f] > 0 &&
-        rep->mx_formats[f].tflops < o.min_mx_tflops[f])
-      rep->mx_rate = "fail";
 }
 
 // ------------------------------------------------------------ dense stage
@@ -1937,149 +1933,6 @@ void dense_expected_tile(int f, uint64_t seed, long w, double* out) {
     dense_expected_tile_as<double>(f, seed, w, out);
   else
     dense_expected_tile_as<float>(f, seed, w, out);
-}
-
-// The tiles in host memory, per format: tiles[f][w * mn * mn + e]. Whatever
-// the device stored (f32, i32 or f64) is held as a double, which every one of
-// them converts to exactly, NaN included; so one judge serves all formats.
-using DenseTiles = std::vector<double>[gpucheck::kDenseFormats];
-
-// Everything after the tiles are in host memory, as judge_mx.
-void judge_dense(DenseTiles& tiles, long nwaves, const Options& o,
-                 Report* rep) {
-  rep->dense_waves = nwaves;
-  std::vector<char> bad(static_cast<size_t>(gpucheck::kDenseFormats) * nwaves, 0);
-  if (o.dump_dense_wave >= 0) {
-    const int f = o.dump_dense_format;
-    const int elems = dense_tile_elems(f);
-    const double* tile = tiles[f].data() + o.dump_dense_wave * elems;
-    for (int e = 0; e < elems; ++e) {
-      const double scaled = tile[e] * gpucheck::kDenseFormatTable[f].scale;
-      // Not a finite integer a long long can hold: null in the dump (the
-      // comparison below finds the wave bad).
-      if (!(scaled >= -9e18 && scaled <= 9e18) ||
-          scaled != static_cast<double>(static_cast<long long>(scaled)))
-        rep->dense_tile.push_back(kDenseNotAnInteger);
-      else
-        rep->dense_tile.push_back(static_cast<long long>(scaled));
-    }
-  }
-  for (const Options::MxInject& m : o.dense_inject)
-    tiles[m.format][m.wave * dense_tile_elems(m.format) + m.elem] += 1.0;
-  std::vector<double> want(32 * 32);
-  bool any = false;
-  for (int f = 0; f < gpucheck::kDenseFormats; ++f) {
-    const int elems = dense_tile_elems(f);
-    const double scale = gpucheck::kDenseFormatTable[f].scale;
-    Report::DenseFormatResult& r = rep->dense_formats[f];
-    for (long w = 0; w < nwaves; ++w) {
-      dense_expected_tile(f, o.seed, w, want.data());
-      const double* tile = tiles[f].data() + w * elems;
-      char& is_bad = bad[static_cast<size_t>(f) * nwaves + w];
-      // Exact by the bounds in gpucheck_pattern.h: == is bit-exactness, and
-      // NaN compares unequal. want holds the value times the scale.
-      for (int e = 0; e < elems && !is_bad; ++e)
-        if (!(tile[e] * scale == want[e])) is_bad = 1;
-      if (is_bad) {
-        if (r.bad_waves == 0) r.first_bad_wave = w;
-        ++r.bad_waves;
-        any = true;
-      }
-    }
-  }
-  rep->dense = any ? "fail" : "pass";
-}
-
-// --cpu: the tiles come from the host product, so this exercises the
-// decoders, judge_dense and the JSON, not a device. No rate is measured.
-void run_dense_cpu(const Options& o, long nwaves, Report* rep) {
-  DenseTiles tiles;
-  std::vector<double> want(32 * 32);
-  for (int f = 0; f < gpucheck::kDenseFormats; ++f) {
-    const int elems = dense_tile_elems(f);
-    tiles[f].resize(static_cast<size_t>(nwaves) * elems);
-    for (long w = 0; w < nwaves; ++w) {
-      dense_expected_tile(f, o.seed, w, want.data());
-      for (int e = 0; e < elems; ++e)
-        tiles[f][w * elems + e] =
-            want[e] / gpucheck::kDenseFormatTable[f].scale;
-    }
-  }
-  judge_dense(tiles, nwaves, o, rep);
-}
-
-// Launches format kFmt's self-test, copies its tiles back into (*tiles)[kFmt]
-// as doubles and its where list into where[kFmt * nwaves ...]; then the next
-// format's.
-template <int kFmt>
-void run_dense_formats(long nwaves, uint64_t seed, DenseTiles* tiles,
-                       std::vector<uint32_t>* where_all) {
-  using Elem = typename DenseTypes<kFmt>::Elem;
-  const size_t n = static_cast<size_t>(nwaves) * dense_tile_elems(kFmt);
-  Elem* dev = nullptr;
-  HIP_CHECK(hipMalloc(&dev, n * sizeof(Elem)));
-  HIP_CHECK(hipMemset(dev, 0xFF, n * sizeof(Elem)));
-  WhereBuffer where(static_cast<size_t>(nwaves));
-  const unsigned int blocks = static_cast<unsigned int>((nwaves + 3) / 4);
-  hipLaunchKernelGGL(dense_selftest<kFmt>, dim3(blocks), dim3(kBlock), 0, 0,
-                     dev, where.dev, static_cast<uint32_t>(nwaves), seed);
-  HIP_CHECK(hipGetLastError());
-  std::vector<Elem> host(n);
-  HIP_CHECK(hipMemcpy(host.data(), dev, n * sizeof(Elem), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(dev));
-  (*tiles)[kFmt].assign(host.begin(), host.end());
-  const std::vector<uint32_t> ran = where.fetch();
-  where_all->insert(where_all->end(), ran.begin(), ran.end());
-  if constexpr (kFmt + 1 < gpucheck::kDenseFormats)
-    run_dense_formats<kFmt + 1>(nwaves, seed, tiles, where_all);
-}
-
-// Median of five timed launches after one warm-up, as time_mx_formats. For
-// i8 the figure is 10^12 integer operations per second.
-template <int kFmt>
-void time_dense_formats(void* sink, unsigned int blocks, const Options& o,
-                        GpuTimer& timer, Report* rep) {
-  using Elem = typename DenseTypes<kFmt>::Elem;
-  constexpr gpucheck::DenseFormat fmt = gpucheck::kDenseFormatTable[kFmt];
-  const uint32_t trips = static_cast<uint32_t>((o.dense_rate_instr + 3) / 4);
-  std::vector<double> times;
-  for (int rep_i = 0; rep_i < 6; ++rep_i) {
-    timer.begin();
-    hipLaunchKernelGGL(dense_rate<kFmt>, dim3(blocks), dim3(kBlock), 0, 0,
-                       static_cast<Elem*>(sink), trips, o.seed);
-    const double s = timer.end();
-    if (rep_i > 0) times.push_back(s);
-  }
-  std::sort(times.begin(), times.end());
-  const double seconds = times[times.size() / 2];
-  const double flop =
-      2.0 * fmt.mn * fmt.mn * fmt.step_k * 4.0 * trips * (blocks * 4.0);
-  rep->dense_formats[kFmt].tflops = seconds > 0 ? flop / seconds / 1e12 : 0.0;
-  rep->dense_formats[kFmt].launch_ms = seconds * 1e3;
-  if constexpr (kFmt + 1 < gpucheck::kDenseFormats)
-    time_dense_formats<kFmt + 1>(sink, blocks, o, timer, rep);
-}
-
-void run_dense(const Options& o, long nwaves, int compute_units, Report* rep) {
-  DenseTiles tiles;
-  run_dense_formats<0>(nwaves, o.seed, &tiles, &rep->dense_where);
-  judge_dense(tiles, nwaves, o, rep);
-
-  // Two workgroups of four waves per compute unit: waves on every SIMD. The
-  // sink holds the widest element, one per lane.
-  const unsigned int blocks =
-      static_cast<unsigned int>(2 * std::max(1, compute_units));
-  void* sink = nullptr;
-  HIP_CHECK(hipMalloc(&sink, static_cast<size_t>(blocks) * kBlock * sizeof(double)));
-  GpuTimer timer;
-  timer.init();
-  time_dense_formats<0>(sink, blocks, o, timer, rep);
-  HIP_CHECK(hipFree(sink));
-  rep->dense_rate = "pass";
-  for (int f = 0; f < gpucheck::kDenseFormats; ++f)
-    if (o.min_dense_tflops[f] > 0 &&
-        rep->dense_formats[f].tflops < o.min_dense_tflops[f])
-      rep->dense_rate = "fail";
 }
 
 // -------------------------------------------------------------- LDS stage
@@ -2321,13 +2174,56 @@ void print_where_list(const char* name, const std::vector<uint32_t>& where,
   printf("],");
 }
 
+// "X_cus_covered":n,"X_simds_covered":n,
+void print_covered(const Family& fam, const Report::TileResult& t) {
+  size_t cus = 0, simds = 0;
+  count_where(t.where, &cus, &simds);
+  printf("\"%s_cus_covered\":%zu,\"%s_simds_covered\":%zu,", fam.prefix, cus,
+         fam.prefix, simds);
+}
+
+// Where the first bad wave of format `f` ran, "" without one.
+std::string first_bad_where(const Report::TileResult& t, int f) {
+  const long w = t.formats[f].first_bad_wave;
+  return w < 0 ? "" : where_of(t.where, f * t.waves + w);
+}
+
+// "X_formats":{"name":{...},...},
+void print_formats(const Family& fam, const Report::TileResult& t,
+                   bool launch_ms) {
+  printf("\"%s_formats\":{", fam.prefix);
+  for (int f = 0; f < fam.formats; ++f) {
+    const Report::TileResult::Format& fr = t.formats[f];
+    printf("%s\"%s\":{\"bad_waves\":%ld,\"first_bad_wave\":%ld,"
+           "\"first_bad_where\":\"%s\",\"tflops\":%.3f",
+           f ? "," : "", fam.names[f], fr.bad_waves, fr.first_bad_wave,
+           first_bad_where(t, f).c_str(), fr.tflops);
+    if (launch_ms) printf(",\"launch_ms\":%.4f", fr.launch_ms);
+    printf("}");
+  }
+  printf("},");
+}
+
+bool all_integers(const std::vector<long long>& dump) {
+  return std::find(dump.begin(), dump.end(), kNotAnInteger) == dump.end();
+}
+
+// [v,v,...], null for a value that is no integer within the family's bound
+void print_tile_values(const std::vector<long long>& dump) {
+  printf("[");
+  for (size_t i = 0; i < dump.size(); ++i)
+    if (dump[i] == kNotAnInteger)
+      printf("%snull", i ? "," : "");
+    else
+      printf("%s%lld", i ? "," : "", dump[i]);
+  printf("]");
+}
+
 void print_report(const Options& o, const Report& r, int code, double wall_s) {
   const bool hbm_fail = r.mismatch_vectors != 0;
-  size_t mfma_cus = 0, mfma_simds = 0, mx_cus = 0, mx_simds = 0;
-  count_where(r.mfma_where, &mfma_cus, &mfma_simds);
-  count_where(r.mx_where, &mx_cus, &mx_simds);
-  size_t dense_cus = 0, dense_simds = 0;
-  count_where(r.dense_where, &dense_cus, &dense_simds);
+  const Report::TileResult& mfma = r.tile[kMfma];
+  const Report::TileResult& mx = r.tile[kMx];
+  const Report::TileResult& dense = r.tile[kDense];
   std::string failed;
   auto add_failed = [&](const char* name) {
     failed += failed.empty() ? "\"" : ",\"";
@@ -2336,13 +2232,13 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
   };
   if (hbm_fail) add_failed("hbm");
   if (!strcmp(r.copy, "fail")) add_failed("copy");
-  if (!strcmp(r.mfma, "fail")) add_failed("mfma");
-  if (!strcmp(r.mx, "fail")) add_failed("mx");
+  if (!strcmp(mfma.verdict, "fail")) add_failed("mfma");
+  if (!strcmp(mx.verdict, "fail")) add_failed("mx");
   if (!strcmp(r.lds, "fail")) add_failed("lds");
-  if (!strcmp(r.dense, "fail")) add_failed("dense");
+  if (!strcmp(dense.verdict, "fail")) add_failed("dense");
   if (!strcmp(r.bandwidth, "fail")) add_failed("bandwidth");
-  if (!strcmp(r.mx_rate, "fail")) add_failed("mx_rate");
-  if (!strcmp(r.dense_rate, "fail")) add_failed("dense_rate");
+  if (!strcmp(mx.rate, "fail")) add_failed("mx_rate");
+  if (!strcmp(dense.rate, "fail")) add_failed("dense_rate");
   if (lds_coverage_required_and_partial(o, r)) add_failed("lds_coverage");
 
   printf("{\"tool\":\"gpucheck\",\"mode\":\"%s\",\"device\":\"%s\","
@@ -2383,7 +2279,8 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
     printf("\"copy_first_bad_offset\":null,\"copy_first_bad_xor\":null,");
   printf("\"mfma\":\"%s\",\"mfma_waves\":%ld,\"mfma_bad_waves\":%ld,"
          "\"mfma_first_bad_wave\":%ld,",
-         r.mfma, r.mfma_waves, r.mfma_bad_waves, r.mfma_first_bad_wave);
+         mfma.verdict, mfma.waves, mfma.formats[0].bad_waves,
+         mfma.formats[0].first_bad_wave);
   if (o.dump_pattern) {
     printf("\"pattern_dump\":[");
     for (size_t i = 0; i < r.pattern_dump.size(); ++i)
@@ -2398,79 +2295,52 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
              r.vector_dump[i].value.c_str());
     printf("],");
   }
-  if (o.dump_mfma_tile >= 0) {
-    if (r.mfma_tile_valid) {
-      printf("\"mfma_tile\":{\"wave\":%ld,\"values\":[", o.dump_mfma_tile);
-      for (size_t i = 0; i < r.mfma_tile.size(); ++i)
-        printf("%s%d", i ? "," : "", r.mfma_tile[i]);
-      printf("]},");
+  const TileOptions& mfma_o = o.tile[kMfma];
+  const TileOptions& mx_o = o.tile[kMx];
+  const TileOptions& dense_o = o.tile[kDense];
+  // A value that is no integer: MFMA and MX print no tile, dense prints null
+  // in its place.
+  if (mfma_o.dump_wave >= 0) {
+    if (all_integers(mfma.dump)) {
+      printf("\"mfma_tile\":{\"wave\":%ld,\"values\":", mfma_o.dump_wave);
+      print_tile_values(mfma.dump);
+      printf("},");
     } else {
       printf("\"mfma_tile\":null,");
     }
   }
-  printf("\"mx\":\"%s\",\"mx_waves\":%ld,\"mx_rate\":\"%s\",\"mx_formats\":{",
-         r.mx, r.mx_waves, r.mx_rate);
-  for (int f = 0; f < gpucheck::kMxFormats; ++f)
-    printf("%s\"%s\":{\"bad_waves\":%ld,\"first_bad_wave\":%ld,"
-           "\"first_bad_where\":\"%s\",\"tflops\":%.3f}",
-           f ? "," : "", gpucheck::kMxFormatTable[f].name,
-           r.mx_formats[f].bad_waves, r.mx_formats[f].first_bad_wave,
-           r.mx_formats[f].first_bad_wave < 0
-               ? ""
-               : where_of(r.mx_where, f * r.mx_waves +
-                                          r.mx_formats[f].first_bad_wave)
-                     .c_str(),
-           r.mx_formats[f].tflops);
-  printf("},");
-  if (o.dump_mx_wave >= 0) {
-    if (r.mx_tile_valid) {
-      printf("\"mx_tile\":{\"format\":\"%s\",\"wave\":%ld,\"values_x16\":[",
-             gpucheck::kMxFormatTable[o.dump_mx_format].name, o.dump_mx_wave);
-      for (size_t i = 0; i < r.mx_tile.size(); ++i)
-        printf("%s%ld", i ? "," : "", r.mx_tile[i]);
-      printf("]},");
+  printf("\"mx\":\"%s\",\"mx_waves\":%ld,\"mx_rate\":\"%s\",", mx.verdict,
+         mx.waves, mx.rate);
+  print_formats(kFamilyTable[kMx], mx, false);
+  if (mx_o.dump_wave >= 0) {
+    if (all_integers(mx.dump)) {
+      printf("\"mx_tile\":{\"format\":\"%s\",\"wave\":%ld,\"values_x16\":",
+             kFamilyTable[kMx].names[mx_o.dump_format], mx_o.dump_wave);
+      print_tile_values(mx.dump);
+      printf("},");
     } else {
       printf("\"mx_tile\":null,");
     }
   }
-  printf("\"mfma_cus_covered\":%zu,\"mfma_simds_covered\":%zu,"
-         "\"mfma_first_bad_where\":\"%s\",\"mx_cus_covered\":%zu,"
-         "\"mx_simds_covered\":%zu,",
-         mfma_cus, mfma_simds,
-         where_of(r.mfma_where, r.mfma_first_bad_wave).c_str(), mx_cus,
-         mx_simds);
+  print_covered(kFamilyTable[kMfma], mfma);
+  printf("\"mfma_first_bad_where\":\"%s\",", first_bad_where(mfma, 0).c_str());
+  print_covered(kFamilyTable[kMx], mx);
   printf("\"clock_mhz\":%d,\"mx_s\":%.4f,\"dense_s\":%.4f,", r.clock_mhz,
-         r.mx_s, r.dense_s);
-  printf("\"dense\":\"%s\",\"dense_waves\":%ld,\"dense_rate\":\"%s\","
-         "\"dense_cus_covered\":%zu,\"dense_simds_covered\":%zu,"
-         "\"dense_rate_instr\":%llu,\"dense_formats\":{",
-         r.dense, r.dense_waves, r.dense_rate, dense_cus, dense_simds,
-         static_cast<unsigned long long>(o.dense_rate_instr));
-  for (int f = 0; f < gpucheck::kDenseFormats; ++f) {
-    const Report::DenseFormatResult& d = r.dense_formats[f];
-    printf("%s\"%s\":{\"bad_waves\":%ld,\"first_bad_wave\":%ld,"
-           "\"first_bad_where\":\"%s\",\"tflops\":%.3f,\"launch_ms\":%.4f}",
-           f ? "," : "", gpucheck::kDenseFormatTable[f].name, d.bad_waves,
-           d.first_bad_wave,
-           d.first_bad_wave < 0
-               ? ""
-               : where_of(r.dense_where, f * r.dense_waves + d.first_bad_wave)
-                     .c_str(),
-           d.tflops, d.launch_ms);
-  }
-  printf("},");
-  if (o.dump_dense_wave >= 0) {
+         mx.seconds, dense.seconds);
+  printf("\"dense\":\"%s\",\"dense_waves\":%ld,\"dense_rate\":\"%s\",",
+         dense.verdict, dense.waves, dense.rate);
+  print_covered(kFamilyTable[kDense], dense);
+  printf("\"dense_rate_instr\":%llu,",
+         static_cast<unsigned long long>(dense_o.rate_instr));
+  print_formats(kFamilyTable[kDense], dense, true);
+  if (dense_o.dump_wave >= 0) {
     const gpucheck::DenseFormat& fmt =
-        gpucheck::kDenseFormatTable[o.dump_dense_format];
+        gpucheck::kDenseFormatTable[dense_o.dump_format];
     printf("\"dense_tile\":{\"format\":\"%s\",\"wave\":%ld,\"rows\":%d,"
-           "\"cols\":%d,\"scale\":%d,\"values\":[",
-           fmt.name, o.dump_dense_wave, fmt.mn, fmt.mn, fmt.scale);
-    for (size_t i = 0; i < r.dense_tile.size(); ++i)
-      if (r.dense_tile[i] == kDenseNotAnInteger)
-        printf("%snull", i ? "," : "");
-      else
-        printf("%s%lld", i ? "," : "", r.dense_tile[i]);
-    printf("]},");
+           "\"cols\":%d,\"scale\":%d,\"values\":",
+           fmt.name, dense_o.dump_wave, fmt.mn, fmt.mn, fmt.scale);
+    print_tile_values(dense.dump);
+    printf("},");
   }
   printf("\"lds\":\"%s\",", r.lds);
   if (!r.lds_skip_reason.empty())
@@ -2512,10 +2382,21 @@ void print_report(const Options& o, const Report& r, int code, double wall_s) {
   }
   if (o.dump_lds_where) {
     print_where_list("lds_where", r.lds_where, 4);
-    print_where_list("mfma_where", r.mfma_where, 1);
+    print_where_list("mfma_where", mfma.where, 1);
   }
   printf("\"wall_s\":%.4f}\n", wall_s);
   fflush(stdout);
+}
+
+// How many waves a family runs on a device of `compute_units`. Under --cpu a
+// family runs only with an explicit --X-waves.
+long tile_waves(const Options& o, int fam, int compute_units) {
+  const long asked = o.tile[fam].waves;
+  if (asked >= 0 || o.cpu) return std::max(asked, 0L);
+  long waves = static_cast<long>(kFamilyTable[fam].waves_per_cu) * compute_units;
+  // An explicit --mfma-waves caps the default, so a small run stays small.
+  if (o.tile[kMfma].waves > 0) waves = std::min(waves, o.tile[kMfma].waves);
+  return waves;
 }
 
 }  // namespace
@@ -2527,74 +2408,57 @@ int main(int argc, char** argv) {
 
   Report rep;
   try {
+    hipDeviceProp_t prop = {};
+    if (!o.cpu) {
+      int count = 0;
+      HIP_CHECK(hipGetDeviceCount(&count));
+      if (count < 1) throw HipError{"no visible GPU"};
+      HIP_CHECK(hipSetDevice(0));
+      HIP_CHECK(hipGetDeviceProperties(&prop, 0));
+      rep.device = std::string(prop.name) + " " + prop.gcnArchName;
+      rep.compute_units = prop.multiProcessorCount;
+      rep.clock_mhz = prop.clockRate / 1000;  // reported in kHz
+    }
+    long waves[kFamilies];
+    for (int fam = 0; fam < kFamilies; ++fam)
+      waves[fam] = tile_waves(o, fam, rep.compute_units);
+    const long lds_groups = o.lds_groups >= 0 || o.cpu
+                                ? std::max(o.lds_groups, 0L)
+                                : 2L * rep.compute_units;
+    auto check_tiles = [&](int fam) {
+      return check_tile_args(kFamilyTable[fam], o.tile[fam], waves[fam]);
+    };
+    if (int rc = check_tiles(kMfma)) return rc;
+    if (int rc = check_tiles(kMx)) return rc;
+    if (int rc = check_lds_args(o, lds_groups)) return rc;
+    if (int rc = check_tiles(kDense)) return rc;
     if (o.cpu) {
-      const long nwaves = o.mfma_waves > 0 ? o.mfma_waves : 0;
-      if (int rc = check_mfma_args(o, nwaves)) return rc;
-      const long mx_waves = o.mx_waves > 0 ? o.mx_waves : 0;
-      if (int rc = check_mx_args(o, mx_waves)) return rc;
-      const long lds_groups = o.lds_groups > 0 ? o.lds_groups : 0;
-      if (int rc = check_lds_args(o, lds_groups)) return rc;
-      const long dense_waves = o.dense_waves > 0 ? o.dense_waves : 0;
-      if (int rc = check_dense_args(o, dense_waves)) return rc;
       CpuBackend be(o);
       if (be.mem == nullptr) {
         fprintf(stderr, "gpucheck: cannot allocate %zu bytes\n", o.bytes);
         return 2;
       }
       run_hbm(be, o, &rep);
-      if (nwaves > 0) run_mfma_cpu(o, nwaves, &rep);
-      if (mx_waves > 0) run_mx_cpu(o, mx_waves, &rep);
+      auto run_tiles_on_host = [&](int fam) {
+        if (waves[fam] > 0)
+          run_tiles_cpu(kFamilyTable[fam], waves[fam], o.tile[fam], o.seed,
+                        &rep.tile[fam]);
+      };
+      run_tiles_on_host(kMfma);
+      run_tiles_on_host(kMx);
       if (lds_groups > 0) run_lds_cpu(o, lds_groups, &rep);
-      if (dense_waves > 0) run_dense_cpu(o, dense_waves, &rep);
+      run_tiles_on_host(kDense);
     } else {
-      int count = 0;
-      HIP_CHECK(hipGetDeviceCount(&count));
-      if (count < 1) throw HipError{"no visible GPU"};
-      HIP_CHECK(hipSetDevice(0));
-      hipDeviceProp_t prop;
-      HIP_CHECK(hipGetDeviceProperties(&prop, 0));
-      rep.device = std::string(prop.name) + " " + prop.gcnArchName;
-      rep.compute_units = prop.multiProcessorCount;
-      const long nwaves =
-          o.mfma_waves > 0 ? o.mfma_waves : 8L * prop.multiProcessorCount;
-      if (int rc = check_mfma_args(o, nwaves)) return rc;
-      // An explicit --mfma-waves caps the default, so a small run stays small.
-      long mx_waves = o.mx_waves;
-      if (mx_waves < 0) {
-        mx_waves = 4L * prop.multiProcessorCount;
-        if (o.mfma_waves > 0) mx_waves = std::min(mx_waves, o.mfma_waves);
-      }
-      if (int rc = check_mx_args(o, mx_waves)) return rc;
-      const long lds_groups =
-          o.lds_groups >= 0 ? o.lds_groups : 2L * prop.multiProcessorCount;
-      if (int rc = check_lds_args(o, lds_groups)) return rc;
-      long dense_waves = o.dense_waves;
-      if (dense_waves < 0) {
-        dense_waves = 4L * prop.multiProcessorCount;
-        if (o.mfma_waves > 0) dense_waves = std::min(dense_waves, o.mfma_waves);
-      }
-      if (int rc = check_dense_args(o, dense_waves)) return rc;
-      rep.clock_mhz = prop.clockRate / 1000;  // reported in kHz
       {
         GpuBackend be(o);
         run_hbm(be, o, &rep);
         run_copy(be, o, &rep);
       }
-      run_mfma(o, nwaves, &rep);
-      auto timed = [](double* seconds, auto&& stage) {
-        const auto s0 = std::chrono::steady_clock::now();
-        stage();
-        *seconds = CpuBackend::since(s0);
-      };
-      if (mx_waves > 0)
-        timed(&rep.mx_s, [&] {
-          run_mx(o, mx_waves, prop.multiProcessorCount, &rep);
-        });
+      const int cus = rep.compute_units;
+      run_tiles<MfmaKernels>(o, waves[kMfma], cus, &rep);
+      if (waves[kMx] > 0) run_tiles<MxKernels>(o, waves[kMx], cus, &rep);
       if (lds_groups > 0) run_lds(o, lds_groups, prop, &rep);
-      if (dense_waves > 0)
-        timed(&rep.dense_s, [&] {
-          run_dense(o, dense_waves, prop.multiProcessorCount, &rep);
-        });
+      if (waves[kDense] > 0) run_tiles<DenseKernels>(o, waves[kDense], cus, &rep);
     }
   } catch (const HipError& e) {
     fprintf(stderr, "gpucheck: %s\n", e.what.c_str());
@@ -2608,13 +2472,13 @@ int main(int argc, char** argv) {
   int code = 0;
   if (rep.mismatch_vectors != 0) code = 20;
   else if (!strcmp(rep.copy, "fail")) code = 23;
-  else if (!strcmp(rep.mfma, "fail")) code = 21;
-  else if (!strcmp(rep.mx, "fail")) code = 24;
+  else if (!strcmp(rep.tile[kMfma].verdict, "fail")) code = 21;
+  else if (!strcmp(rep.tile[kMx].verdict, "fail")) code = 24;
   else if (!strcmp(rep.lds, "fail")) code = 26;
-  else if (!strcmp(rep.dense, "fail")) code = 28;
+  else if (!strcmp(rep.tile[kDense].verdict, "fail")) code = 28;
   else if (!strcmp(rep.bandwidth, "fail")) code = 22;
-  else if (!strcmp(rep.mx_rate, "fail")) code = 25;
-  else if (!strcmp(rep.dense_rate, "fail")) code = 29;
+  else if (!strcmp(rep.tile[kMx].rate, "fail")) code = 25;
+  else if (!strcmp(rep.tile[kDense].rate, "fail")) code = 29;
   else if (lds_coverage_required_and_partial(o, rep)) code = 27;
   const double wall_s =
       std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

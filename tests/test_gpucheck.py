@@ -19,28 +19,13 @@ from k8s_runpod_kubelet_amd.gpu.binder import Binder, BindRequest, PlacementErro
 from k8s_runpod_kubelet_amd.gpu.diagnostics import (
     DiagnosticsManager, GpuBusyError, GpuCheckResult, UnknownGpuError,
     run_gpucheck)
+from tests import gpucheck_helpers
 from tests import gpucheck_reference as ref
 from tests.conftest import wait_until
+from tests.gpucheck_helpers import gpucheck, run_cpu  # noqa: F401 (fixture)
 
 
 # ------------------------------------------------------------------ binary
-
-@pytest.fixture(scope="module")
-def gpucheck():
-    from k8s_runpod_kubelet_amd.ops import build
-
-    path = build.build_gpucheck()
-    assert path == build.gpucheck_path() and path.exists()
-    assert os.access(path, os.X_OK)
-    return str(path)
-
-
-def run_cpu(binary, *args):
-    proc = subprocess.run([binary, "--cpu", *map(str, args)],
-                          capture_output=True, text=True, timeout=60)
-    lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
-    return proc.returncode, (json.loads(lines[-1]) if lines else None)
-
 
 def test_builds_through_ops_build(gpucheck):
     from k8s_runpod_kubelet_amd.ops import build, gpucheck_binary
@@ -317,6 +302,26 @@ def write_stub(tmp_path, name, body):
     path.write_text("#!/bin/sh\n" + body)
     path.chmod(path.stat().st_mode | stat.S_IXUSR)
     return str(path)
+
+
+def test_gpu_guard_skips_after_a_child_exits_11(tmp_path, monkeypatch):
+    """The GPU files' runner and guard, with a stub for the binary and a
+    list of this test's own: no GPU is touched, and the real list stays
+    clean."""
+    suspect = []
+    monkeypatch.setattr(gpucheck_helpers, "_card_suspect", suspect)
+    gpucheck_helpers.skip_if_card_suspect()  # nothing happened yet: no skip
+    good = write_stub(tmp_path, "good", "echo '{\"ok\":true,\"big\":[1,2]}'\n")
+    assert gpucheck_helpers.run_gpu(good, "--x", 1, hide=("big",))[:2] == \
+        (0, {"ok": True, "big": [1, 2]})
+    assert suspect == []
+    stub = write_stub(tmp_path, "hip_error", "echo '{\"ok\":false}'\nexit 11\n")
+    with pytest.raises(pytest.fail.Exception, match="gpucheck exit 11"):
+        gpucheck_helpers.run_gpu(stub, "--bytes", 16)
+    assert len(suspect) == 1 and suspect[0].startswith("exit 11:")
+    assert stub in suspect[0]
+    with pytest.raises(pytest.skip.Exception, match="ended badly: exit 11"):
+        gpucheck_helpers.skip_if_card_suspect()
 
 
 @pytest.fixture

@@ -16,23 +16,14 @@ from k8s_runpod_kubelet_amd.gpu.diagnostics import (
     DENSE_FORMATS, EXIT_STAGES, DiagnosticsManager, GpuCheckResult,
     dense_floor_args, first_bad_dense, run_gpucheck)
 from tests import gpucheck_dense_reference as ref
+from tests import gpucheck_helpers
+from tests.gpucheck_helpers import gpucheck  # noqa: F401 (fixture)
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
 
 
-@pytest.fixture(scope="module")
-def gpucheck():
-    from k8s_runpod_kubelet_amd.ops import build
-
-    return str(build.build_gpucheck())
-
-
 def run_cpu(binary, *args):
-    proc = subprocess.run([binary, "--cpu", "--bytes", "4096",
-                           *map(str, args)],
-                          capture_output=True, text=True, timeout=60)
-    lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
-    return proc.returncode, (json.loads(lines[-1]) if lines else None)
+    return gpucheck_helpers.run_cpu(binary, "--bytes", 4096, *args)
 
 
 # ------------------------------------------------------------ reference

@@ -5,71 +5,27 @@ and floor, and one check through the DiagnosticsManager.
 
 As in test_gpucheck_mx_gpu.py, every test starts the binary as a fresh child
 with a 60 s limit of its own, and once a child ends with a HIP error (11), a
-signal or its time limit the rest of the file skips."""
+signal or its time limit the remaining gpucheck GPU tests skip."""
 
-import json
 import math
-import os
-import subprocess
-import time
 
 import pytest
 
 from tests import gpucheck_dense_reference as ref
+from tests import gpucheck_helpers
+from tests.gpucheck_helpers import (  # noqa: F401 (fixtures)
+    CHILD_TIMEOUT_S, _card_suspect, _stop_after_trouble, binary)
 
 pytestmark = pytest.mark.gpu
 
-CHILD_TIMEOUT_S = 60
 # A small run: 5 waves per matrix stage, no MX and no LDS stage.
 SMALL = ["--mfma-waves", 5, "--mx-waves", 0, "--lds-groups", 0]
-
-_card_suspect = []  # reason, once a child ended badly
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_trouble():
-    if not os.path.exists("/dev/kfd"):
-        pytest.skip("no /dev/kfd on this box")
-    if _card_suspect:
-        pytest.skip(f"an earlier gpucheck child ended badly: {_card_suspect[0]}")
-
-
-@pytest.fixture(scope="module")
-def binary():
-    from k8s_runpod_kubelet_amd.ops import gpucheck_binary
-
-    return gpucheck_binary()
 
 
 def run_gpu(binary, *args):
     """-> (exit code, parsed last stdout line); always --bytes 4096."""
-    argv = [binary, "--bytes", "4096", *map(str, args)]
-    t0 = time.monotonic()
-    proc = subprocess.Popen(argv, stdin=subprocess.DEVNULL,
-                            stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                            text=True, start_new_session=True)
-    try:
-        out, err = proc.communicate(timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        _card_suspect.append(f"timeout: {argv}")
-        try:
-            os.killpg(proc.pid, 9)
-        except ProcessLookupError:
-            pass
-        proc.communicate()
-        pytest.fail(f"gpucheck exceeded {CHILD_TIMEOUT_S} s: {argv}")
-    wall = time.monotonic() - t0
-    if proc.returncode == 11 or proc.returncode < 0:
-        _card_suspect.append(f"exit {proc.returncode}: {argv}")
-        pytest.fail(f"gpucheck exit {proc.returncode}: {argv}\n{out}\n{err}")
-    lines = [ln for ln in out.splitlines() if ln.strip()]
-    assert lines, err
-    data = json.loads(lines[-1])
-    shown = dict(data)
-    shown.pop("dense_tile", None)
-    print(f"{' '.join(map(str, args))} -> rc={proc.returncode} "
-          f"wall={wall:.3f}s {json.dumps(shown)}")
-    return proc.returncode, data
+    return gpucheck_helpers.run_gpu(binary, "--bytes", 4096, *args,
+                                    hide=("dense_tile",))[:2]
 
 
 _seen = {}  # compute_units, once a child has reported it

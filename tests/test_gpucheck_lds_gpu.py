@@ -6,21 +6,18 @@ coverage, and where the MFMA and MX tiles ran.
 
 As in test_gpucheck_mx_gpu.py, every test starts the binary as a fresh child
 with a 60 s limit of its own, and once a child ends with a HIP error (11), a
-signal or its time limit the rest of the file skips. The coverage cases need
-a GPU that runs nothing else, as gpucheck has in production."""
-
-import json
-import os
-import subprocess
-import time
+signal or its time limit the remaining gpucheck GPU tests skip. The coverage
+cases need a GPU that runs nothing else, as gpucheck has in production."""
 
 import pytest
 
+from tests import gpucheck_helpers
 from tests import gpucheck_lds_reference as ref
+from tests.gpucheck_helpers import (  # noqa: F401 (fixtures)
+    _stop_after_trouble, binary)
 
 pytestmark = pytest.mark.gpu
 
-CHILD_TIMEOUT_S = 60
 SEED = ref.DEFAULT_SEED
 # The smallest region the binary accepts, four MFMA waves, no MX stage.
 SMALL = ["--bytes", "16", "--mfma-waves", "4", "--mx-waves", "0"]
@@ -39,53 +36,11 @@ KEYS_BEFORE = {
     "mx_formats", "wall_s"}
 MX_FORMAT_KEYS_BEFORE = {"bad_waves", "first_bad_wave", "tflops"}
 
-_card_suspect = []  # reason, once a child ended badly
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_trouble():
-    if not os.path.exists("/dev/kfd"):
-        pytest.skip("no /dev/kfd on this box")
-    if _card_suspect:
-        pytest.skip(f"an earlier gpucheck child ended badly: {_card_suspect[0]}")
-
-
-@pytest.fixture(scope="module")
-def binary():
-    from k8s_runpod_kubelet_amd.ops import gpucheck_binary
-
-    return gpucheck_binary()
-
 
 def run_gpu(binary, *args):
     """-> (exit code, parsed last stdout line)."""
-    argv = [binary, *map(str, args)]
-    t0 = time.monotonic()
-    proc = subprocess.Popen(argv, stdin=subprocess.DEVNULL,
-                            stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                            text=True, start_new_session=True)
-    try:
-        out, err = proc.communicate(timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        _card_suspect.append(f"timeout: {argv}")
-        try:
-            os.killpg(proc.pid, 9)
-        except ProcessLookupError:
-            pass
-        proc.communicate()
-        pytest.fail(f"gpucheck exceeded {CHILD_TIMEOUT_S} s: {argv}")
-    wall = time.monotonic() - t0
-    if proc.returncode == 11 or proc.returncode < 0:
-        _card_suspect.append(f"exit {proc.returncode}: {argv}")
-        pytest.fail(f"gpucheck exit {proc.returncode}: {argv}\n{out}\n{err}")
-    lines = [ln for ln in out.splitlines() if ln.strip()]
-    assert lines, err
-    data = json.loads(lines[-1])
-    shown = {k: v for k, v in data.items()
-             if k not in ("lds_where", "mfma_where")}
-    print(f"{' '.join(map(str, args))} -> rc={proc.returncode} "
-          f"wall={wall:.3f}s {json.dumps(shown)}")
-    return proc.returncode, data
+    return gpucheck_helpers.run_gpu(binary, *args,
+                                    hide=("lds_where", "mfma_where"))[:2]
 
 
 @pytest.mark.parametrize("pass_", [0, 1])

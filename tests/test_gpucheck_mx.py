@@ -15,22 +15,13 @@ from k8s_runpod_kubelet_amd.config import Config, load_config
 from k8s_runpod_kubelet_amd.gpu.diagnostics import (
     EXIT_STAGES, DiagnosticsManager, GpuCheckResult, first_bad_mx,
     mx_floor_args, run_gpucheck)
+from tests import gpucheck_helpers
 from tests import gpucheck_mx_reference as ref
-
-
-@pytest.fixture(scope="module")
-def gpucheck():
-    from k8s_runpod_kubelet_amd.ops import build
-
-    return str(build.build_gpucheck())
+from tests.gpucheck_helpers import gpucheck  # noqa: F401 (fixture)
 
 
 def run_cpu(binary, *args):
-    proc = subprocess.run([binary, "--cpu", "--bytes", "4096",
-                           *map(str, args)],
-                          capture_output=True, text=True, timeout=60)
-    lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
-    return proc.returncode, (json.loads(lines[-1]) if lines else None)
+    return gpucheck_helpers.run_cpu(binary, "--bytes", 4096, *args)
 
 
 # ------------------------------------------------------------ reference

@@ -5,67 +5,23 @@ through the DiagnosticsManager.
 
 As in test_gpucheck_gpu.py, every test starts the binary as a fresh child
 with a 60 s limit of its own, and once a child ends with a HIP error (11), a
-signal or its time limit the rest of the file skips."""
+signal or its time limit the remaining gpucheck GPU tests skip."""
 
-import json
 import math
-import os
-import subprocess
-import time
 
 import pytest
 
+from tests import gpucheck_helpers
 from tests import gpucheck_mx_reference as ref
+from tests.gpucheck_helpers import (  # noqa: F401 (fixtures)
+    CHILD_TIMEOUT_S, _card_suspect, _stop_after_trouble, binary)
 
 pytestmark = pytest.mark.gpu
-
-CHILD_TIMEOUT_S = 60
-
-_card_suspect = []  # reason, once a child ended badly
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_trouble():
-    if not os.path.exists("/dev/kfd"):
-        pytest.skip("no /dev/kfd on this box")
-    if _card_suspect:
-        pytest.skip(f"an earlier gpucheck child ended badly: {_card_suspect[0]}")
-
-
-@pytest.fixture(scope="module")
-def binary():
-    from k8s_runpod_kubelet_amd.ops import gpucheck_binary
-
-    return gpucheck_binary()
 
 
 def run_gpu(binary, *args):
     """-> (exit code, parsed last stdout line); always --bytes 4096."""
-    argv = [binary, "--bytes", "4096", *map(str, args)]
-    t0 = time.monotonic()
-    proc = subprocess.Popen(argv, stdin=subprocess.DEVNULL,
-                            stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                            text=True, start_new_session=True)
-    try:
-        out, err = proc.communicate(timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        _card_suspect.append(f"timeout: {argv}")
-        try:
-            os.killpg(proc.pid, 9)
-        except ProcessLookupError:
-            pass
-        proc.communicate()
-        pytest.fail(f"gpucheck exceeded {CHILD_TIMEOUT_S} s: {argv}")
-    wall = time.monotonic() - t0
-    if proc.returncode == 11 or proc.returncode < 0:
-        _card_suspect.append(f"exit {proc.returncode}: {argv}")
-        pytest.fail(f"gpucheck exit {proc.returncode}: {argv}\n{out}\n{err}")
-    lines = [ln for ln in out.splitlines() if ln.strip()]
-    assert lines, err
-    data = json.loads(lines[-1])
-    print(f"{' '.join(map(str, args))} -> rc={proc.returncode} "
-          f"wall={wall:.3f}s {lines[-1]}")
-    return proc.returncode, data
+    return gpucheck_helpers.run_gpu(binary, "--bytes", 4096, *args)[:2]
 
 
 _seen = {}  # compute_units, once a child has reported it
